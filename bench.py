@@ -13,8 +13,18 @@ the whole pipeline before the timed region.  value = executed RK4 main-loop
 steps of all ranks / max-over-ranks wall time of the K timed frames (inputs
 resident in HBM, sky uploaded once).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, spins the clock up, warms up, times the K steps and prints
+the line (metric, value, ms_per_step, the configuration, the in-region kernel
+times).  --dump-outputs DIR also writes the last timed frame and the step
+count as DIR/*.npy (dump_outputs), for comparing two builds output for
+output.  --full adds everything else the bench measures and checks, each in a
+pass of its own outside the timed region: the diagnostic pass and the
+roofline, the compute-only pass, isolated-launch kernel times, the link probe
+(N > 1), the frame check, the CPU baseline with its comparator, the
+reference-equivalent fan cost and the `ring_f64` record.
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the
 N rank processes itself (launch_ranks, before anything touches the GPU),
@@ -45,6 +55,10 @@ NEWTON_EVALS = 3  # per sphere crossing (sphere_ray_tracer.rs:129)
 # estimate and its h^2 scaling, 67 for a Newton evaluation (no estimate)
 FLOPS_PER_ATTEMPT = 77
 FLOPS_PER_NEWTON_DP5 = 67
+# --dump-outputs: a frame above this many bytes as float32 is written as a
+# seeded sample of its pixels (the 4K frame: 133 MB whole)
+DUMP_MAX_BYTES = 48 << 20
+DUMP_SEED = 20240607
 
 
 def parse():
@@ -52,6 +66,17 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="beside the metric's line also measure and check everything else: the diagnostic pass and "
+                        "the roofline, the compute-only pass, the isolated-launch kernel times, the present link "
+                        "probe (N > 1), the frame check, the CPU baseline, the reference-equivalent fan cost and "
+                        "the `ring_f64` record.  Without it a run sets up, spins the clock up, warms up, times the "
+                        "K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step produced as DIR/<name>.npy: rank 0's "
+                        "frame as assembled for present (rgba.npy: float32 (H, W, 4), or a fixed seeded sample of "
+                        "its pixels, (n, 4), when the frame is larger than %d MB as float32) and the timed "
+                        "region's step count (steps_total.npy: float64 (1,))" % (DUMP_MAX_BYTES >> 20))
     p.add_argument("--spinup-frames", type=int, default=300,
                    help="untimed GPU clock spin-up frames x n_gpus before the warmup steps (the clock settles "
                         "after ~100 full frames); a frame count, identical on every rank")
@@ -91,7 +116,7 @@ def parse():
                    help="N = 1: also time the K frames on two render streams (consecutive frames overlap) and report "
                         "it as `pipelined`; off by default, since rocprofv3 would average the overlapped launches "
                         "into the kernel's duration")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=16)
     p.add_argument("--cpu-row-step", type=int, default=None,
                    help="CPU baseline sample: every k-th row (default 1 up to 4K, 4 above)")
@@ -104,9 +129,9 @@ def parse():
                    help="GEO_FLAG_RING_F64 on every frame: the capture band's lanes integrate in f64 inside the "
                         "render kernel (direct or adaptive mode; batched launches too).  Without it an N = 1 "
                         "direct/adaptive line still measures the mode beside the metric, as its `ring_f64` record")
-    p.add_argument("--no-ring-record", action="store_true", help="skip the `ring_f64` record")
+    p.add_argument("--no-ring-record", action="store_true", help="--full: skip the `ring_f64` record")
     p.add_argument("--no-frame-check", action="store_true",
-                   help="skip rank 0's check, after the timed region, that every frame of the timed run's last "
+                   help="--full: skip rank 0's check, after the timed region, that every frame of the timed run's last "
                         "batch (the frames as assembled for present) equals a single-launch render of the frame; "
                         "by default it runs and a mismatch exits non-zero")
     p.add_argument("--check-frame", action="store_true", help=argparse.SUPPRESS)  # the default since round 3
@@ -127,6 +152,8 @@ def parse():
     args = p.parse_args()
     if args.share is not None and args.gpus != 1:
         p.error("--share emulates one rank's share on one GPU: --gpus 1 only")
+    if args.share is not None and args.dump_outputs:
+        p.error("--dump-outputs writes the assembled frame; --share renders one rank's bands only")
     return args
 
 
@@ -384,7 +411,7 @@ def main():
     # metric; the fastest by max-over-ranks wall time is used for the timed
     # region.  Every rank holds the same all-reduced times, so all pick alike.
     lead_trials = None
-    link_probe = present_link_probe(sf, dist, args) if world > 1 else None
+    link_probe = present_link_probe(sf, dist, args) if world > 1 and args.full else None
     if len(leads) > 1:
         spin_up(sf, args.spinup_frames * world)  # the trials compare layouts at the settled clock
         times = []
@@ -429,54 +456,59 @@ def main():
         counts its steps in the context) or without (the warmup)."""
         return (None, None) if moving is None else (moving[i][0], moving[i][2 if defer else 1])
 
-    # untimed diagnostic pass: per-pixel steps + mask give the RK4 evaluations
-    # per launch (main-loop steps + 3 Newton evaluations per sphere crossing);
-    # with --motion, of every timed frame (per-frame totals on the device)
-    n_loc = max(1, L.packed_rows()) * W
-    diag_mask = torch.zeros(n_loc, dtype=torch.uint8, device=dev)
-    diag_steps = torch.zeros(n_loc, dtype=torch.int32, device=dev)
-    diag_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
-    diag_uv = torch.zeros(n_loc * 2, dtype=torch.float32, device=dev) if mode == g.GEO_MODE_FAN else None
-    sf.render_local(sf.bufs[0], out_mask=diag_mask, out_uv=diag_uv, out_steps=diag_steps, steps_total=diag_ctr)
-    per_frame = None  # --motion: [(steps, hits)] of each timed frame
-    if moving is not None:
-        f_steps = torch.zeros(args.steps, dtype=torch.int64, device=dev)
-        f_hits = torch.zeros(args.steps, dtype=torch.int64, device=dev)
-        m_mask = torch.zeros_like(diag_mask)
-        m_steps = torch.zeros_like(diag_steps)
-        for i in range(args.steps):
-            fr, sc = moving[args.warmup + i][:2]
-            sf.render_local(sf.bufs[1], scene=sc, frame=fr, out_mask=m_mask, out_steps=m_steps,
-                            steps_total=f_steps[i:i + 1])
-            f_hits[i] = ((m_mask == 0) & (m_steps > 0)).sum()
-        per_frame = list(zip(f_steps.tolist(), f_hits.tolist()))
-        del m_mask, m_steps
-    torch.cuda.synchronize()
-    # the fan-mode draw is a memory-side kernel: its algorithmic bytes are the
-    # RGBA8 it writes plus the distinct sky texels its rows sample (and the fan)
-    sky_touch = None
-    if mode == g.GEO_MODE_FAN:
-        valid = torch.zeros(n_loc, dtype=torch.bool, device=dev)
-        valid.view(-1, W)[: L.rows_mine()] = True  # the packed rows this rank renders
-        sky_touch = sky_bytes_touched(diag_uv.view(-1, 2), (diag_mask == 0) & valid, sky.shape[1], sky.shape[0])
-        del valid
-    st = diag_steps.to(torch.int64)
-    hits = int(((diag_mask == 0) & (st > 0)).sum().item())  # unwritten (clipped) rows are 0
-    rows_mine = L.rows_mine()
-    steps_diag = int(diag_ctr.item())
-
     def flops_of(steps, hits):
         if mode == g.GEO_MODE_ADAPTIVE:
             return FLOPS_PER_ATTEMPT * steps + FLOPS_PER_NEWTON_DP5 * NEWTON_EVALS * hits
         return FLOPS_PER_EVAL * (steps + NEWTON_EVALS * hits)
 
-    if per_frame is None:
-        per_frame = [(steps_diag, hits)] * args.steps
-    frame_flops = [flops_of(st_, h_) for st_, h_ in per_frame]
-    steps_timed = sum(st_ for st_, _ in per_frame)  # what the timed region must count
-    # per-launch figures: the average timed frame (one pose: the diagnostic frame's)
-    evals_per_launch = round(sum(st_ + NEWTON_EVALS * h_ for st_, h_ in per_frame) / args.steps)
-    flops_per_launch = flops_mean = sum(frame_flops) / args.steps
+    rows_mine = L.rows_mine()
+
+    # --full: an untimed diagnostic pass: per-pixel steps + mask give the RK4
+    # evaluations per launch (main-loop steps + 3 Newton evaluations per sphere
+    # crossing); with --motion, of every timed frame (per-frame totals on the
+    # device): per_frame = [(steps, hits)] of each timed frame
+    per_frame = frame_flops = steps_timed = sky_touch = None
+    evals_per_launch = 0
+    if args.full:
+        n_loc = max(1, L.packed_rows()) * W
+        diag_mask = torch.zeros(n_loc, dtype=torch.uint8, device=dev)
+        diag_steps = torch.zeros(n_loc, dtype=torch.int32, device=dev)
+        diag_ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        diag_uv = torch.zeros(n_loc * 2, dtype=torch.float32, device=dev) if mode == g.GEO_MODE_FAN else None
+        sf.render_local(sf.bufs[0], out_mask=diag_mask, out_uv=diag_uv, out_steps=diag_steps,
+                        steps_total=diag_ctr)
+        if moving is not None:
+            f_steps = torch.zeros(args.steps, dtype=torch.int64, device=dev)
+            f_hits = torch.zeros(args.steps, dtype=torch.int64, device=dev)
+            m_mask = torch.zeros_like(diag_mask)
+            m_steps = torch.zeros_like(diag_steps)
+            for i in range(args.steps):
+                fr, sc = moving[args.warmup + i][:2]
+                sf.render_local(sf.bufs[1], scene=sc, frame=fr, out_mask=m_mask, out_steps=m_steps,
+                                steps_total=f_steps[i:i + 1])
+                f_hits[i] = ((m_mask == 0) & (m_steps > 0)).sum()
+            per_frame = list(zip(f_steps.tolist(), f_hits.tolist()))
+            del m_mask, m_steps
+        torch.cuda.synchronize()
+        # the fan-mode draw is a memory-side kernel: its algorithmic bytes are the
+        # RGBA8 it writes plus the distinct sky texels its rows sample (and the fan)
+        if mode == g.GEO_MODE_FAN:
+            valid = torch.zeros(n_loc, dtype=torch.bool, device=dev)
+            valid.view(-1, W)[: L.rows_mine()] = True  # the packed rows this rank renders
+            sky_touch = sky_bytes_touched(diag_uv.view(-1, 2), (diag_mask == 0) & valid, sky.shape[1],
+                                          sky.shape[0])
+            del valid
+        st = diag_steps.to(torch.int64)
+        hits = int(((diag_mask == 0) & (st > 0)).sum().item())  # unwritten (clipped) rows are 0
+        steps_diag = int(diag_ctr.item())
+
+        if per_frame is None:
+            per_frame = [(steps_diag, hits)] * args.steps
+        frame_flops = [flops_of(st_, h_) for st_, h_ in per_frame]
+        steps_timed = sum(st_ for st_, _ in per_frame)  # what the timed region must count
+        # per-launch figures: the average timed frame (one pose: the diagnostic frame's)
+        evals_per_launch = round(sum(st_ + NEWTON_EVALS * h_ for st_, h_ in per_frame) / args.steps)
+        flops_per_launch = flops_mean = sum(frame_flops) / args.steps
 
     # timed region: K frames; steps counted in the context (GEO_FLAG_DEFER_STEPS)
     # and flushed once at the end; fence-free event pairs on every k-th frame
@@ -520,32 +552,38 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    # compute-only pass (SURVEY.md §8e asks for compute-only and end-to-end
-    # scaling): the same K frames, rendered on the same streams, without the
-    # RGB24 pack, the gather or the reassembly
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    c0 = time.perf_counter()
-    if sf.batch:
-        for i0 in range(0, args.steps, sf.K):
-            n_b = min(sf.K, args.steps - i0)
-            if moving is None:
-                sf.render_batch((i0 // sf.K) % 2, [frame] * n_b, scene=scene_defer)
-            else:
-                mb = moving[args.warmup + i0:args.warmup + i0 + n_b]
-                sf.render_batch((i0 // sf.K) % 2, [m[0] for m in mb], scenes=[m[2] for m in mb])
-    else:
-        for i in range(args.steps):
-            fr, sc = pose(args.warmup + i)
-            with torch.cuda.stream(sf._render_stream(i)):
-                sf.render_local(sf.local_view(i), scene=scene_defer if sc is None else sc, frame=fr)
-    sf._join()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed_compute = time.perf_counter() - c0
-    ctx.steps_flush(torch.zeros(1, dtype=torch.int64, device=dev))  # discard this pass's steps
+    steps_done = int(steps_ctr.item())
+    # --dump-outputs: the last timed frame leaves the device now (the passes
+    # below render into the same buffers); the files are written at the end
+    dump_frame = sf.frame_rgba().cpu().numpy() if args.dump_outputs and rank == 0 else None
+    elapsed_compute = 0.0
+    if args.full:
+        # compute-only pass (SURVEY.md §8e asks for compute-only and end-to-end
+        # scaling): the same K frames, rendered on the same streams, without the
+        # RGB24 pack, the gather or the reassembly
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        c0 = time.perf_counter()
+        if sf.batch:
+            for i0 in range(0, args.steps, sf.K):
+                n_b = min(sf.K, args.steps - i0)
+                if moving is None:
+                    sf.render_batch((i0 // sf.K) % 2, [frame] * n_b, scene=scene_defer)
+                else:
+                    mb = moving[args.warmup + i0:args.warmup + i0 + n_b]
+                    sf.render_batch((i0 // sf.K) % 2, [m[0] for m in mb], scenes=[m[2] for m in mb])
+        else:
+            for i in range(args.steps):
+                fr, sc = pose(args.warmup + i)
+                with torch.cuda.stream(sf._render_stream(i)):
+                    sf.render_local(sf.local_view(i), scene=scene_defer if sc is None else sc, frame=fr)
+        sf._join()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed_compute = time.perf_counter() - c0
+        ctx.steps_flush(torch.zeros(1, dtype=torch.int64, device=dev))  # discard this pass's steps
     # N = 1, informational: the same K frames with two render streams, so
     # that frame i+1's waves fill frame i's tail (what a frame loop gains
     # from pipelining; not the metric's value, whose launches do not overlap)
@@ -562,11 +600,11 @@ def main():
         el2 = time.perf_counter() - p0
         ctx.steps_flush(torch.zeros(1, dtype=torch.int64, device=dev))  # discard this pass's steps
         pipelined = {"render_streams": 2, "ms_per_step": el2 / args.steps * 1e3,
-                     "value": steps_diag * args.steps / el2,
+                     "value": steps_done / el2,
                      "what": "the same K frames on two render streams (consecutive frames overlap); informational"}
         del sf2
     per_launch = 1  # frames per timed launch
-    if sf.S > 1 or sf.batch:
+    if args.full and (sf.S > 1 or sf.batch):
         # one launch at a time: 20 launches back to back on ONE stream (no
         # overlap, and no idle gap between them that would let the clock
         # drop), an event pair around each, one sync at the end; with batched
@@ -596,13 +634,12 @@ def main():
         evs = {i: ab for i, ab in enumerate(iso)}
         per_launch = sf.K if sf.batch else 1
     kernel_ms = sorted(a.elapsed_time(b) / per_launch for a, b in evs.values())
-    kernel_ms_avg = sum(kernel_ms) / len(kernel_ms)
-    if moving is not None and not (sf.S > 1 or sf.batch):
+    kernel_ms_avg = sum(kernel_ms) / len(kernel_ms) if kernel_ms else 0.0  # none: isolated launches are --full's
+    if args.full and moving is not None and not (sf.S > 1 or sf.batch):
         # the event-timed frames' own flops over their own times
         flops_per_launch = sum(frame_flops[i] for i in evs) / len(evs)
 
-    steps_done = int(steps_ctr.item())
-    if steps_done != steps_timed:
+    if args.full and steps_done != steps_timed:
         raise SystemExit(f"step counter mismatch: {steps_done} vs {steps_timed} counted by the diagnostic pass")
     stats = torch.tensor([elapsed, kernel_ms_avg, elapsed_compute], dtype=torch.float64, device=rdev)
     tot = torch.tensor([steps_done, rows_mine * W * args.steps, evals_per_launch], dtype=torch.int64, device=rdev)
@@ -615,19 +652,20 @@ def main():
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         per_rank = {"ms_per_step": [round(float(t[0]) / args.steps * 1e3, 5) for t in every],
-                    "compute_only_ms_per_step": [round(float(t[1]) / args.steps * 1e3, 5) for t in every],
-                    "kernel_ms_avg": [round(float(t[2]), 5) for t in every],
                     "rows": [int(t[3]) for t in every]}
+        if args.full:
+            per_rank["compute_only_ms_per_step"] = [round(float(t[1]) / args.steps * 1e3, 5) for t in every]
+            per_rank["kernel_ms_avg"] = [round(float(t[2]), 5) for t in every]
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     elapsed_max, kernel_ms_max, compute_max = float(stats[0]), float(stats[1]), float(stats[2])
     total_steps, total_pixels, evals_all = (int(x) for x in tot.tolist())
 
-    # rank 0, outside the timed region: the frames of the timed run's last
+    # --full, rank 0, outside the timed region: the frames of the timed run's last
     # batch, as assembled for present from every rank's bands (RCCL gather +
     # geo_assemble_lead at N > 1), against a single-launch render of the frame
     frame_check = None
-    if not args.no_frame_check and rank == 0 and args.share is None:
+    if args.full and not args.no_frame_check and rank == 0 and args.share is None:
         # the last timed frame's own pose (with --motion each frame has its own)
         ref = torch.empty(H * W * 4, dtype=torch.uint8, device=dev)
         if moving is None:
@@ -668,14 +706,6 @@ def main():
         return
 
     value = total_steps / elapsed_max if mode != g.GEO_MODE_FAN else total_pixels / elapsed_max
-    # roofline for the dominant kernel, on this rank: algorithmic flops per
-    # launch / avg launch time (event pairs on the kernel's own dispatch, the
-    # execution time a profiler's timestamps give), and the same flops per
-    # frame of the compute-only pass's wall time (no events; launch gaps
-    # included)
-    achieved_tflops = flops_per_launch / (kernel_ms_avg * 1e-3) / 1e12
-    wall_tflops = flops_mean / (compute_max / args.steps) / 1e12
-    pmc_file, pmc = pmc_profile(args.config, args.mode, world) if not args.mips else (None, {})
     if mode == g.GEO_MODE_FAN:
         metric = (f"pixels/sec at {W}x{H}, fan-mode draw (the reference's display path: 400-node fan lerp, "
                   f"shader.wgsl:77-105; whole job)")
@@ -736,53 +766,70 @@ def main():
         "frames_per_s": args.steps / elapsed_max,
         "steps_per_frame": total_steps // args.steps,
         "mean_steps_per_pixel": total_steps / total_pixels,
-        "kernel_ms": {"avg": kernel_ms_avg, "median": kernel_ms[len(kernel_ms) // 2], "min": kernel_ms[0],
-                      "max_over_ranks_avg": kernel_ms_max, "frames_timed": len(kernel_ms),
-                      "events": ("event pairs on the render kernel's own dispatch (geo_time_next_render: "
-                                 "start/end of its execution, no marker packets) on every %d-th timed frame"
-                                 % args.event_every if sf.S == 1 and not sf.batch else
-                                 "event pairs on the render kernel's own dispatch (geo_time_next_render) on 20 "
-                                 "launches back to back on one stream after the timed region (%d render streams "
-                                 "overlap consecutive frames inside it)" % sf.S if not sf.batch else
-                                 "event pairs on the render kernel's own dispatch (geo_time_next_render) on 20 "
-                                 "batched launches of %d frames back to back on one stream after the timed region, "
-                                 "each launch's time / %d (the timed region renders each gather batch in one launch)"
-                                 % (sf.K, sf.K))},
         "pipelined": pipelined,
-        "link_probe": link_probe,
-        "compute_only": {"value": (total_steps if mode != g.GEO_MODE_FAN else total_pixels) / compute_max, "ms_per_step": compute_max / args.steps * 1e3,
-                         "what": "the same K frames rendered on the same streams without pack, gather or "
-                                 "reassembly (max over ranks)"},
         "spinup_frames": spin,
-        "roofline": {
-            "bound": "valu",
-            "achieved": achieved_tflops,
-            "peak": PEAK_FP32_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": achieved_tflops / PEAK_FP32_TFLOPS,
-            "traffic": pmc.get("traffic_bytes"),
-            "kernel": f"geo_render_kernel<{mode}>",
-            "flops": ("reference-equivalent algorithmic FP32 flops (FMA = 2): %s; the kernel executes fewer "
-                      "instructions for the same arithmetic (14 VALU per RK4 step), so frac is not hardware VALU "
-                      "utilisation: see hw_fp32_tflops_pmc and valu_per_simd_cycle_pmc"
-                      % ("77 per RK5(4) attempt, 67 per Newton evaluation" if mode == g.GEO_MODE_ADAPTIVE else
-                         "40 per RK4 evaluation of the reference's literal form, SURVEY.md §8d")),
-            "algorithmic_flops_per_launch": flops_per_launch,
-            "evals_per_launch": evals_per_launch,
-            "achieved_wall": wall_tflops,
-            "frac_wall": wall_tflops / PEAK_FP32_TFLOPS,
-            "wall": "flops per launch / (compute-only wall time per frame): no event pairs, launch gaps included",
-            "hw_fp32_tflops_pmc": pmc.get("hw_fp32_tflops"),
-            "valu_per_simd_cycle_pmc": pmc.get("valu_per_simd_cycle"),
-            "pmc_profile": pmc_file,
-        },
+        "full": bool(args.full),
     }
-    out["roofline"]["trace_check"] = trace_profile(out["config"]["workload"], world) if not args.share else None
-    if mode == g.GEO_MODE_FAN:
-        out["roofline"] = fan_roofline(sky_touch, rows_mine * W, kernel_ms_avg, compute_max / args.steps * 1e3, pmc,
-                                       pmc_file, mode)
-    cpu_ok = True
-    if world == 1 and not args.no_cpu_baseline:
+    if kernel_ms:  # in-region event pairs (one render stream); isolated launches are --full's
+        out["kernel_ms"] = {"avg": kernel_ms_avg, "median": kernel_ms[len(kernel_ms) // 2], "min": kernel_ms[0],
+                            "max_over_ranks_avg": kernel_ms_max, "frames_timed": len(kernel_ms),
+                            "events": ("event pairs on the render kernel's own dispatch (geo_time_next_render: "
+                                       "start/end of its execution, no marker packets) on every %d-th timed frame"
+                                       % args.event_every if sf.S == 1 and not sf.batch else
+                                       "event pairs on the render kernel's own dispatch (geo_time_next_render) on 20 "
+                                       "launches back to back on one stream after the timed region (%d render streams "
+                                       "overlap consecutive frames inside it)" % sf.S if not sf.batch else
+                                       "event pairs on the render kernel's own dispatch (geo_time_next_render) on 20 "
+                                       "batched launches of %d frames back to back on one stream after the timed region, "
+                                       "each launch's time / %d (the timed region renders each gather batch in one launch)"
+                                       % (sf.K, sf.K))}
+    cpu_ok = ring_ok = True
+    if args.full:
+        # roofline for the dominant kernel, on this rank: algorithmic flops per
+        # launch / avg launch time (event pairs on the kernel's own dispatch, the
+        # execution time a profiler's timestamps give), and the same flops per
+        # frame of the compute-only pass's wall time (no events; launch gaps
+        # included)
+        achieved_tflops = flops_per_launch / (kernel_ms_avg * 1e-3) / 1e12
+        wall_tflops = flops_mean / (compute_max / args.steps) / 1e12
+        pmc_file, pmc = pmc_profile(args.config, args.mode, world) if not args.mips else (None, {})
+        out.update({
+            "link_probe": link_probe,
+            "compute_only": {"value": (total_steps if mode != g.GEO_MODE_FAN else total_pixels) / compute_max,
+                             "ms_per_step": compute_max / args.steps * 1e3,
+                             "what": "the same K frames rendered on the same streams without pack, gather or "
+                                     "reassembly (max over ranks)"},
+            "roofline": {
+                "bound": "valu",
+                "achieved": achieved_tflops,
+                "peak": PEAK_FP32_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": achieved_tflops / PEAK_FP32_TFLOPS,
+                "traffic": pmc.get("traffic_bytes"),
+                "kernel": f"geo_render_kernel<{mode}>",
+                "flops": ("reference-equivalent algorithmic FP32 flops (FMA = 2): %s; the kernel executes fewer "
+                          "instructions for the same arithmetic (14 VALU per RK4 step), so frac is not hardware VALU "
+                          "utilisation: see hw_fp32_tflops_pmc and valu_per_simd_cycle_pmc"
+                          % ("77 per RK5(4) attempt, 67 per Newton evaluation" if mode == g.GEO_MODE_ADAPTIVE else
+                             "40 per RK4 evaluation of the reference's literal form, SURVEY.md §8d")),
+                "algorithmic_flops_per_launch": flops_per_launch,
+                "evals_per_launch": evals_per_launch,
+                "achieved_wall": wall_tflops,
+                "frac_wall": wall_tflops / PEAK_FP32_TFLOPS,
+                "wall": "flops per launch / (compute-only wall time per frame): no event pairs, launch gaps "
+                        "included",
+                "hw_fp32_tflops_pmc": pmc.get("hw_fp32_tflops"),
+                "valu_per_simd_cycle_pmc": pmc.get("valu_per_simd_cycle"),
+                "pmc_profile": pmc_file,
+            },
+        })
+        out["roofline"]["trace_check"] = (trace_profile(out["config"]["workload"], world) if not args.share
+                                          else None)
+        if mode == g.GEO_MODE_FAN:
+            out["roofline"] = fan_roofline(sky_touch, rows_mine * W, kernel_ms_avg, compute_max / args.steps * 1e3,
+                                           pmc, pmc_file, mode)
+        out["frame_check"] = frame_check
+    if args.full and world == 1 and not args.no_cpu_baseline:
         fan = None
         if mode == g.GEO_MODE_FAN:  # the fan the draws read, as the host's copy
             fan = ctx.solve_ray_fan(cfg.sphere_r, cfg.rs, cfg.max_steps, cfg.step, 400, obs.get_radial_position())
@@ -791,12 +838,12 @@ def main():
         cpu_ok = out["cpu_baseline"]["matches_gpu"]["ok"]
         if mode != g.GEO_MODE_FAN:
             out["reference_equivalent"] = reference_fan_cost(ctx, cfg, obs.get_radial_position())
-    out["frame_check"] = frame_check
-    ring_ok = True
-    if (world == 1 and mode != g.GEO_MODE_FAN and not args.ring_f64 and not args.mips and not args.share
+    if (args.full and world == 1 and mode != g.GEO_MODE_FAN and not args.ring_f64 and not args.mips and not args.share
             and args.motion == "none" and not args.no_ring_record and cfg.rs > 0.0):
         out["ring_f64"] = ring_record(g, ctx, frame, scene, sky, W, H, args, flops_of, dev)
         ring_ok = out["ring_f64"]["matches_cpu"]["ok"]
+    if dump_frame is not None:
+        out["dumped"] = dump_outputs(args.dump_outputs, dump_frame.reshape(H, W, 4), total_steps)
     print(json.dumps(out), flush=True)
     if not ring_ok and not os.environ.get("GEO_AB_VARIANT"):  # (A/B runs of non-specification variants)
         raise SystemExit("ring_f64: the GPU's band rows differ from the CPU path's (matches_cpu)")
@@ -806,6 +853,29 @@ def main():
         dist.destroy_process_group()
     if not frame_ok:
         raise SystemExit("frame check failed: an assembled frame differs from the single-launch frame")
+
+
+def dump_outputs(path: str, rgba, steps_total: int) -> dict:
+    """--dump-outputs: the last timed frame (rgba: (H, W, 4) uint8, as rank 0
+    holds it for present) and the timed region's step count as path/<name>.npy.
+    A frame above DUMP_MAX_BYTES as float32 is written as a sample of its
+    pixels: DUMP_MAX_BYTES / 16 distinct pixels drawn once with DUMP_SEED (the
+    same pixels for every run of the same frame size), in frame order."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    h, w = rgba.shape[:2]
+    n = DUMP_MAX_BYTES // 16
+    if h * w > n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=n, replace=False))
+        rgba = rgba.reshape(h * w, 4)[idx]
+        what = f"{n} of the {w}x{h} frame's pixels (seed {DUMP_SEED}, frame order)"
+    else:
+        what = f"the whole {w}x{h} frame"
+    np.save(os.path.join(path, "rgba.npy"), rgba.astype(np.float32))
+    np.save(os.path.join(path, "steps_total.npy"), np.array([steps_total], dtype=np.float64))
+    return {"dir": path, "rgba.npy": what + ", RGBA8 as float32", "steps_total.npy": "RK4 steps (adaptive: "
+            "attempts) all ranks executed in the timed region (the value's numerator), float64"}
 
 
 def sky_bytes_touched(uv, sampled, tw: int, th: int) -> dict:

@@ -1,9 +1,10 @@
 """bench.py's contract (the driver parses its one JSON line).
 
 CPU: the committed PMC traffic is attached only to the workload it was taken
-on.  GPU: a short run (the driver's own --steps/--warmup shape, fewer spin-up
-frames) prints one JSON line with every field the contract names, and its
-numbers are consistent with each other.
+on.  GPU: a short --full run (the driver's own --steps/--warmup shape, fewer
+spin-up frames) prints one JSON line with every field the contract names, and
+its numbers are consistent with each other; a plain run prints the metric's
+line alone and --dump-outputs writes the last timed frame.
 """
 import json
 import os
@@ -35,7 +36,7 @@ def test_bench_short_run_prints_the_contract_line():
 
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
                         "--spinup-frames", "60", "--cpu-row-step", "8"],
                        cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -61,6 +62,81 @@ def test_bench_short_run_prints_the_contract_line():
     assert len(cb["seconds_per_run"]) == 3
     # the frames of the timed run's last batch equal a single-launch frame
     assert d["frame_check"]["ok"] is True and d["frame_check"]["frames"] >= 1
+
+
+def test_dump_outputs_whole_frame_or_seeded_sample(tmp_path):
+    """--dump-outputs' writer: float32/float64 .npy files, the whole frame when
+    it fits DUMP_MAX_BYTES as float32, else the same seeded pixels every run;
+    at most 64 MB in all."""
+    import numpy as np
+
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 256, (9, 13, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), small, 12345678901)
+    got = np.load(tmp_path / "a" / "rgba.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    st = np.load(tmp_path / "a" / "steps_total.npy")
+    assert st.dtype == np.float64 and st.tolist() == [12345678901.0]
+    # the 4K frame (133 MB as float32): a sample, identical from run to run
+    h, w = 2160, 3840
+    big = (np.arange(h * w * 4, dtype=np.uint32) % 251).astype(np.uint8).reshape(h, w, 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 1)
+    b, c = np.load(tmp_path / "b" / "rgba.npy"), np.load(tmp_path / "c" / "rgba.npy")
+    n = bench.DUMP_MAX_BYTES // 16
+    assert b.dtype == np.float32 and b.shape == (n, 4) and np.array_equal(b, c)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(h * w, size=n, replace=False))
+    assert len(np.unique(idx)) == n and np.array_equal(b, big.reshape(-1, 4)[idx].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 64 << 20
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_line_alone_and_dumps_the_last_frame(tmp_path):
+    """Without --full: the metric's line with ms_per_step and none of the
+    separate passes' records; --dump-outputs writes the last timed frame,
+    equal to a single-launch render of the same frame, and the step count."""
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_sky
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                        "--config", "cfg2_1080p", "--spinup-frames", "10", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["full"] is False and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["steps_per_frame"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "ring_f64", "roofline", "compute_only", "frame_check", "reference_equivalent"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["rgba.npy", "steps_total.npy"]
+    cfg = CONFIGS["cfg2_1080p"]
+    W, H = cfg.width, cfg.height
+    rgba = np.load(out / "rgba.npy")
+    assert rgba.dtype == np.float32 and rgba.shape == (H, W, 4)
+    steps = np.load(out / "steps_total.npy")
+    assert steps.dtype == np.float64 and steps[0] == 6 * d["steps_per_frame"]
+    obs = g.Observer(cfg.rs, cfg.fov, W, H)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg.step, cfg.max_steps)
+    ctx = g.Context(0)
+    ctx.set_sky(make_sky(cfg.sky, cfg.sky_size))
+    ref = torch.empty(H * W * 4, dtype=torch.uint8, device="cuda:0")
+    total = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    ctx.render_rows(obs.calc_transformation_pipeline(), scene, W, H, 0, H, ref, steps_total=total)
+    torch.cuda.synchronize()
+    assert np.array_equal(rgba, ref.cpu().numpy().reshape(H, W, 4).astype(np.float32))
+    assert int(total.item()) == d["steps_per_frame"]
 
 
 def test_rank0_lead_specs_and_trials():
@@ -143,7 +219,7 @@ def test_bench_two_ranks_gloo_frame_check():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--config", "cfg2_1080p", "--steps", "8", "--warmup", "2", "--spinup-frames", "4",
+                        "--full", "--config", "cfg2_1080p", "--steps", "8", "--warmup", "2", "--spinup-frames", "4",
                         "--lead-trial-frames", "8", "--frames-per-gather", "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -9,17 +9,17 @@
 #   suite            pytest -m gpu (one process) + smoke()
 #   tests:<k-expr>   pytest -m gpu -k <k-expr>
 #   gloo8 | gloo:N   the driver's N-rank form (N = 8 for gloo8) on this one GPU with gloo:
-#                    bench.py --gpus 8 --dist-backend gloo --steps 20 --warmup 5
+#                    bench.py --full --gpus 8 --dist-backend gloo --steps 20 --warmup 5
 #                    (self-launcher, --rank0-lead auto, batched launches,
 #                    frame_check), its wall time recorded
 #   bench:<cfg>[:<mode>[:<steps>]]
-#                    bench.py under rocprofv3 --kernel-trace --stats, the
+#                    bench.py --full under rocprofv3 --kernel-trace --stats, the
 #                    bench line and the trace's timed-window average from the
 #                    SAME invocation (tools/trace_window.py)
-#   plain:<cfg>[:<mode>[:<steps>]]   bench.py alone (default flags)
+#   plain:<cfg>[:<mode>[:<steps>]]   bench.py --full alone (no profiler)
 #                    (bench and plain: BENCH_ARGS="..." adds bench.py flags, e.g. --ring-f64)
 #   pmc:<cfg>[:<mode>]  the PMC passes (each its own rocprofv3 run)
-#   motion           bench.py --motion none|orbit|fall x --dispatch learned|natural, N = 1 and --share 1/8
+#   motion           bench.py --full --motion none|orbit|fall x --dispatch learned|natural, N = 1 and --share 1/8
 #   timeline[:cases] tools/wave_timeline.py: every wave's span in a launch (diagnostic build)
 #   ab:<cfgs>[:reps] interleaved A/B of LIBS="a.so b.so" and/or ABARGS="args;args" (bench lines;
 #                    configs comma-separated; replaces the round-5 fpl_ab.sh / batch_ab.sh)
@@ -57,7 +57,7 @@ for step in "$@"; do
       n=${a1:-8}; [ $kind = gloo8 ] && n=8
       heartbeat
       t0=$(date +%s.%N)
-      timeout -k 10 1000 python3 bench.py --gpus $n --dist-backend gloo --steps 20 --warmup 5 \
+      timeout -k 10 1000 python3 bench.py --full --gpus $n --dist-backend gloo --steps 20 --warmup 5 \
         > "$OUT/gloo${n}_bench.json" 2> "$OUT/gloo${n}_bench.err"
       rc=$?
       t1=$(date +%s.%N)
@@ -65,7 +65,7 @@ for step in "$@"; do
       python3 - "$OUT" "$t0" "$t1" "$rc" "$n" <<'EOF'
 import json, sys
 out, t0, t1, rc, n = sys.argv[1], float(sys.argv[2]), float(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
-rec = {"cmd": f"python3 bench.py --gpus {n} --dist-backend gloo --steps 20 --warmup 5", "rc": rc,
+rec = {"cmd": f"python3 bench.py --full --gpus {n} --dist-backend gloo --steps 20 --warmup 5", "rc": rc,
        "wall_s": round(t1 - t0, 2), "driver_timeout_s": 600}
 try:
     d = json.loads(open(f"{out}/gloo{n}_bench.json").read().strip().splitlines()[-1])
@@ -80,7 +80,7 @@ EOF
       [ $rc -eq 0 ] || { tail -20 "$OUT/gloo${n}_bench.err"; exit $rc; } ;;
     bench|plain)
       cfg=${a1:-cfg3_4k}; mode=${a2:-}; steps=${a3:-20}
-      margs="--config $cfg --steps $steps --warmup 5 ${BENCH_ARGS:-}"; [ -n "$mode" ] && margs="$margs --mode $mode"
+      margs="--full --config $cfg --steps $steps --warmup 5 ${BENCH_ARGS:-}"; [ -n "$mode" ] && margs="$margs --mode $mode"
       name=${cfg}${mode:+_$mode}
       if [ $kind = plain ]; then
         timeout -k 10 400 python3 bench.py $margs > "$OUT/${name}_bench.json" 2> "$OUT/${name}_bench.err"
@@ -132,7 +132,7 @@ PY
             for disp in learned natural; do
               sargs=""; [ $shr != none ] && sargs="--share $shr --frames-per-gather 8 --batch-launch on"
               f="$OUT/motion_${mot}_${disp}_${shr/\//of}_$rep.json"
-              timeout -k 10 200 python3 bench.py --motion $mot --dispatch $disp --steps 200 --warmup 20 \
+              timeout -k 10 200 python3 bench.py --full --motion $mot --dispatch $disp --steps 200 --warmup 20 \
                 --no-cpu-baseline $sargs > "$f" 2> "$f.err"
               rc=$?; [ $rc -eq 0 ] || { tail -5 "$f.err"; exit $rc; }
               echo "$rep $shr $mot $disp $(python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1]); print(d['ms_per_step'], d['kernel_ms']['avg'], d['value'])" "$f")" \
@@ -161,7 +161,7 @@ PY
           for xa in "${argsets[@]}"; do
             for v in $libs; do
               cp "$v" "$LIB"
-              GEO_AB_VARIANT=1 timeout -k 10 300 python3 bench.py $cargs $xa --no-cpu-baseline --steps 200 > "$OUT/ab.json" 2> "$OUT/ab.err"
+              GEO_AB_VARIANT=1 timeout -k 10 300 python3 bench.py --full $cargs $xa --no-cpu-baseline --steps 200 > "$OUT/ab.json" 2> "$OUT/ab.err"
               rc=$?; [ $rc -eq 0 ] || { tail -5 "$OUT/ab.err"; cp "$OUT/.orig.so" "$LIB"; exit $rc; }
               python3 -c "
 import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1])

@@ -11,7 +11,7 @@ i=0
 for SET in "$@"; do
   i=$((i+1))
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d "$OUT/${TAG}_$i" -o run \
-     -- python3 "$ROOT/bench.py" --steps 5 --warmup 1 --spinup-frames 10 --no-cpu-baseline --config "${CONFIG:-cfg3_4k}" ${EXTRA_ARGS:-} > "$OUT/${TAG}_$i.log" 2>&1
+     -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 1 --spinup-frames 10 --no-cpu-baseline --config "${CONFIG:-cfg3_4k}" ${EXTRA_ARGS:-} > "$OUT/${TAG}_$i.log" 2>&1
   rc=$?; echo "pass $i ($SET) rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/${TAG}_$i.log"; exit $rc; fi
 done

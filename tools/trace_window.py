@@ -1,7 +1,7 @@
 """Average duration of the render kernel over bench.py's timed region, from a
-rocprofv3 --kernel-trace CSV of `bench.py` (N = 1, one render stream).
+rocprofv3 --kernel-trace CSV of `bench.py --full` (N = 1, one render stream).
 
-bench.py launches the render kernel in this order: 1 diagnostic frame, the
+bench.py --full launches the render kernel in this order: 1 diagnostic frame, the
 clock spin-up (--spinup-frames), the warmup, the K timed frames, then the K
 compute-only frames.  rocprofv3's --stats average covers all of them (the
 spin-up frames run while the clock ramps); this prints the average over the
