@@ -50,7 +50,11 @@ extern "C" {
                                    no context memory), in GEO_MODE_ADAPTIVE too; steps_total
                                    counts the band's f64 steps;
                                 8: GEO_RING_X 5e-3 (was 8e-3); GEO_FLAG_RING_F64 in batched
-                                   launches (geo_render_band_set_frames / _batch) */
+                                   launches (geo_render_band_set_frames / _batch);
+                                   (still 8, additions only, announced by GEO_HAS_DISK:
+                                   GEO_FLAG_DISK, geo_set_disk, geo_clear_disk,
+                                   geo_disk_hits_next_render) */
+#define GEO_HAS_DISK 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -110,6 +114,29 @@ typedef enum geo_status {
                                    GEO_MODE_FAN, GEO_FLAG_COMPOSITE or GEO_FLAG_MIPS
                                    (GEO_EINVAL). */
 #define GEO_RING_X 5e-3f  /* (8e-3 before ABI 8; tools/ring_width_margin.py) */
+#define GEO_FLAG_DISK 16u       /* (a build extension, not in the reference) draw the context's
+                                   thin accretion disk (geo_set_disk) over the frame: a ray
+                                   meets the disk plane at the traveled angles a_0 + k pi,
+                                   k < GEO_DISK_MAX_CROSSINGS (the direct image, the secondary
+                                   image over the shadow, the third one at the photon ring);
+                                   crossing k is a hit when the main loop integrated that far
+                                   (before its exit by crossing, escape, horizon or budget)
+                                   and r_in <= r <= r_out there.  The hits' level-0 samples
+                                   of the disk texture are blended far to near (k = 2, 1, 0)
+                                   with the reference's 8-bit alpha blend over what the plain
+                                   render writes; mask, UV, steps and steps_total are the
+                                   plain render's (csrc/geo_disk.h).
+                                   geo_render_rows / _bands / _band_set only, GEO_MODE_DIRECT,
+                                   with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
+                                   and rs < r_in; r_out < sphere_r and r_obs < sphere_r
+                                   (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
+                                   A ray the reference ends before its loop (its pre-filters
+                                   and radial cases: an observer inside the photon sphere)
+                                   draws no disk.  Follow-ups, not in this ABI: GEO_FLAG_RING_F64
+                                   on disk frames, the batched entry points and multi-GPU
+                                   launches, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE,
+                                   Doppler and redshift shading. */
+#define GEO_DISK_MAX_CROSSINGS 3
 
 /* Observer motion states, ObserverState (SR/simulation/observer.rs:12-16). */
 #define GEO_OBSERVER_UNMOVING 0
@@ -178,6 +205,36 @@ void geo_ctx_destroy(geo_ctx* ctx);
  * sum over l < 4 of (max(1, w >> l) + 2) * (max(1, h >> l) + 2) * 4 < 2^31,
  * w, h <= 2^20 (GEO_EINVAL otherwise). */
 int geo_set_sky(geo_ctx* ctx, const uint8_t* rgba8, uint32_t w, uint32_t h);
+
+/* The thin accretion disk of GEO_FLAG_DISK renders: the annulus r_in..r_out
+ * of the plane through the centre with normal `normal`, in the sky texture's
+ * frame (the frame central_to_uv maps to; the observer sits at r_obs times
+ * central_to_uv's third column there).  Texture coordinates: U = the azimuth
+ * in turns from `axis` (projected into the plane) towards normal x axis,
+ * V = (r - r_in) / (r_out - r_in). */
+typedef struct geo_disk {
+    float r_in, r_out;
+    float normal[3];
+    float axis[3];
+} geo_disk;
+
+/* Sets the context's disk and uploads its RGBA8 texture (row-major, w*h*4
+ * bytes, host memory; copied synchronously after this context's renders in
+ * flight, as geo_set_sky does; sampled at level 0: U wraps, V clamps, 8-bit
+ * sub-texel weights; a texture with alpha gives a translucent disk).
+ * w, h <= 2^20 and (w + 2) * (h + 2) * 4 < 2^31.  GEO_EINVAL for
+ * !(0 < r_in < r_out), a zero normal, or an axis parallel to the normal (or
+ * zero); a refused call leaves the context's disk as it was.  After a failed
+ * upload (GEO_EHIP, GEO_ENOMEM) the context has no disk. */
+int geo_set_disk(geo_ctx* ctx, const geo_disk* disk, const uint8_t* rgba8, uint32_t w, uint32_t h);
+/* Removes the disk (GEO_FLAG_DISK renders return GEO_ESTATE again). */
+int geo_clear_disk(geo_ctx* ctx);
+/* The next render of this context writes its disk hits to out_hits (device,
+ * nrows*width*3*2 floats, laid out as the render's rows): slot k of a pixel
+ * holds (r, U) of crossing k, or (0, 0) when that crossing is not a hit.
+ * Consumed by the next render call whether it succeeds or not (the idiom of
+ * geo_time_next_render); a render without GEO_FLAG_DISK writes nothing. */
+int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
 
 /* Uploads a ray fan of n >= 2 nodes (host memory, copied synchronously after
  * the last solve and draws of the buffer it goes to; geo_solve_ray_fan

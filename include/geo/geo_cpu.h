@@ -43,6 +43,20 @@ int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, const uint8_t
                    uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
                    float* out_uv, uint32_t* out_steps, unsigned long long* steps_total);
 
+/* geo_render_cpu with the thin disk of GEO_FLAG_DISK (geo.h): scene->flags
+ * must carry GEO_FLAG_DISK (geo_render_cpu itself rejects it), under the
+ * rules of geo_render_rows and geo_set_disk.  disk_rgba8: the disk texture
+ * (row-major RGBA8, host, disk_w x disk_h); out_hits (optional, host):
+ * nrows*width*3*2 floats, the layout of geo_disk_hits_next_render.  Through
+ * the kernel's header (csrc/geo_disk.h): output equal to the GPU's bit for
+ * bit. */
+int geo_render_cpu_disk(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8, uint32_t sky_w,
+                        uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width, uint32_t height,
+                        uint32_t row0, uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8,
+                        uint8_t* out_mask, float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                        const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h,
+                        float* out_hits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -279,6 +279,15 @@ struct Image {
     std::vector<uint8_t> rgba;
 };
 
+// A thin accretion disk for BasicSphereBuffer::set_thin_disk (GEO_FLAG_DISK, a
+// build extension): the annulus r_in..r_out of the plane with `normal` in the
+// sky texture's frame, azimuth 0 along `axis` (geo_set_disk).
+struct ThinDisk {
+    Image texture;
+    float r_in = 0.0f, r_out = 0.0f;
+    Vec3 normal{0.0f, 0.0f, 1.0f}, axis{1.0f, 0.0f, 0.0f};
+};
+
 // ---- BasicSphereBuffer (basic_sphere_buffer.rs) -------------------------
 class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
    public:
@@ -319,6 +328,15 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
         if (mode_ == GEO_MODE_FAN) ray_tracer_.update_device_fan(radial_position, stream);
     }
 
+    // The ray-traced thin disk drawn with this sphere (geo_set_disk): when the
+    // sphere is a pass's first, in direct mode with the level-0 sampler and
+    // without ring_f64 (GEO_FLAG_DISK's rules, geo.h).
+    void set_thin_disk(const ThinDisk& d) {
+        const geo_disk gd{d.r_in, d.r_out, {d.normal.x, d.normal.y, d.normal.z}, {d.axis.x, d.axis.y, d.axis.z}};
+        check(geo_set_disk(ctx_->get(), &gd, d.texture.rgba.data(), d.texture.width, d.texture.height), "geo_set_disk");
+        disk_ = true;
+    }
+
     // SchwarzschildSphereShaderDraw::draw (:92-100) + fs_main over the pass's target
     void draw(RenderPass& pass) const override {
         if (!(radial_position_ > 0.0)) throw Error("BasicSphereBuffer::draw before update_ray_fan", GEO_ESTATE);
@@ -331,6 +349,7 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
         s.mode = mode_;
         s.flags = (pass.cleared ? 0u : GEO_FLAG_COMPOSITE) | (mipmaps_ ? GEO_FLAG_MIPS : 0u) |
                   (ring_f64_ ? GEO_FLAG_RING_F64 : 0u);
+        if (disk_ && s.flags == 0u && mode_ == GEO_MODE_DIRECT) s.flags = GEO_FLAG_DISK;
         s.tol = 0.0f;
         check(geo_render_rows(ctx_->get(), &pass.uniform, &s, pass.width, pass.height, 0, pass.height, pass.target,
                               nullptr, nullptr, nullptr, nullptr, pass.stream),
@@ -348,6 +367,7 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
     uint32_t mode_;
     bool mipmaps_;
     bool ring_f64_;
+    bool disk_ = false;
     double radial_position_ = 0.0;
 };
 

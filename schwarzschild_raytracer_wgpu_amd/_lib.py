@@ -30,6 +30,8 @@ GEO_FLAG_DEFER_STEPS = 1
 GEO_FLAG_COMPOSITE = 2
 GEO_FLAG_MIPS = 4
 GEO_FLAG_RING_F64 = 8
+GEO_FLAG_DISK = 16
+GEO_DISK_MAX_CROSSINGS = 3
 GEO_RING_X = 5e-3
 GEO_MAX_BATCH_FRAMES = 8
 
@@ -67,6 +69,17 @@ class GeoScene(ctypes.Structure):
     ]
 
 
+class GeoDisk(ctypes.Structure):
+    """geo_disk: the thin accretion disk of GEO_FLAG_DISK renders."""
+
+    _fields_ = [
+        ("r_in", ctypes.c_float),
+        ("r_out", ctypes.c_float),
+        ("normal", ctypes.c_float * 3),
+        ("axis", ctypes.c_float * 3),
+    ]
+
+
 assert ctypes.sizeof(GeoFrame) == 208
 assert ctypes.sizeof(GeoScene) == 32
 
@@ -82,6 +95,9 @@ SIGNATURES = {
     "geo_ctx_create": (_int, [_int, ctypes.POINTER(_vp)]),
     "geo_ctx_destroy": (None, [_vp]),
     "geo_set_sky": (_int, [_vp, _vp, _u32, _u32]),
+    "geo_set_disk": (_int, [_vp, ctypes.POINTER(GeoDisk), _vp, _u32, _u32]),
+    "geo_clear_disk": (_int, [_vp]),
+    "geo_disk_hits_next_render": (_int, [_vp, _vp]),
     "geo_set_fan": (_int, [_vp, _vp, _u32]),
     "geo_solve_ray_fan": (_int, [_vp, _f64, _f64, _u32, _f64, _u32, _f64, _vp, _vp]),
     "geo_render_rows": (

@@ -133,6 +133,31 @@ class Context:
             raise ValueError("sky must be an (h, w, 4) uint8 array")
         check("geo_set_sky", lib.geo_set_sky(self._h, a.ctypes.data, a.shape[1], a.shape[0]))
 
+    def set_disk(self, rgba8: np.ndarray, r_in: float, r_out: float, normal=(0.0, 0.0, 1.0),
+                 axis=(1.0, 0.0, 0.0)) -> None:
+        """geo_set_disk: the thin accretion disk GEO_FLAG_DISK renders draw, the annulus
+        r_in..r_out of the plane with `normal` (sky-texture frame), textured by an
+        (h, w, 4) uint8 array: U = azimuth in turns from `axis`, V = (r - r_in)/(r_out - r_in)."""
+        a = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("disk texture must be an (h, w, 4) uint8 array")
+        d = _lib.GeoDisk(r_in, r_out, (ctypes.c_float * 3)(*normal), (ctypes.c_float * 3)(*axis))
+        check("geo_set_disk", lib.geo_set_disk(self._h, ctypes.byref(d), a.ctypes.data, a.shape[1], a.shape[0]))
+
+    def clear_disk(self) -> None:
+        check("geo_clear_disk", lib.geo_clear_disk(self._h))
+
+    def disk_hits_next_render(self, buf) -> None:
+        """geo_disk_hits_next_render: the next render writes 3 x (r, U) floats per pixel
+        of its rows into `buf` (a contiguous float32 device tensor; the caller sizes it
+        nrows*width*6)."""
+        _check_buffer("buf", buf, 0, None)
+        import torch
+
+        if buf.dtype != torch.float32:
+            raise ValueError("buf must be float32")
+        check("geo_disk_hits_next_render", lib.geo_disk_hits_next_render(self._h, _ptr(buf)))
+
     def set_fan(self, fan: np.ndarray) -> None:
         a = np.ascontiguousarray(fan, dtype=np.float32)
         check("geo_set_fan", lib.geo_set_fan(self._h, a.ctypes.data, a.size))

@@ -12,6 +12,7 @@
 
 #include "../../include/geo/geo_cpu.h"
 #include "geo_band.h"
+#include "geo_disk.h"
 #include "geo_pixel.h"
 
 namespace {
@@ -39,6 +40,13 @@ struct CpuJob {
     // GEO_FLAG_RING_F64 (geo_band.h): the band's f64 constants, when it applies
     bool ring;
     geo::BandConsts band;
+    // geo_render_cpu_disk (geo_disk.h): the disk's constants, its texture and
+    // the optional hit slots
+    bool disk;
+    geo::DiskConsts dk;
+    const uint32_t* dtex;
+    uint32_t dw, dh;
+    float* hits;
 };
 
 float geodesic(const CpuJob& j, float st, float ct, float rct, uint32_t* n) {
@@ -145,9 +153,57 @@ unsigned long long run_rows_mips(const CpuJob& j, unsigned tid, unsigned nthread
     return total;
 }
 
+// The disk frame's rows (GEO_MODE_DIRECT, level-0 sampler, no composite):
+// the kernel's geo_render_disk_kernel per pixel.
+unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthreads) {
+    unsigned long long total = 0;
+    const float psi_k = j.f->psi_factor_and_position[0];
+    auto fetch = [sky = j.sky](uint32_t i) { return sky[i]; };
+    auto dfetch = [t = j.dtex](uint32_t i) { return t[i]; };
+    auto dsample = [&](float U, float V) { return geo::sample_sky_raw(dfetch, j.dw, j.dh, U, V); };
+    const geo::PixelConsts& k = j.k;
+    for (uint32_t ly = tid; ly < j.nrows; ly += nthreads) {
+        const uint32_t py = j.row0 + ly * j.row_step;
+        for (uint32_t px = 0; px < j.width; ++px) {
+            float c2x, c2y, c2z;
+            geo::pixel_central_dir(j.cam, j.f->movement_to_central, psi_k, j.kt, px, py, &c2x, &c2y, &c2z);
+            const float st = geo::central_sin(c2z);
+            const float ct = geo::central_rho(c2x, c2y);
+            const float rct = geo::rcpf_(ct);
+            geo::DiskRay dr;
+            geo::disk_ray(j.dk, k, c2x, c2y, ct, rct, &dr);
+            uint32_t n = 0;
+            float Uk[geo::kDiskMaxCrossings];
+            float ang;
+            switch (geo::geodesic_kind(k)) {
+                case geo::kCurvedOut: ang = geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk); break;
+                case geo::kCurvedIn: ang = geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk); break;
+                default: ang = geo::geodesic_angle_disk<geo::kFlat>(k, st, ct, rct, dr, &n, Uk);
+            }
+            const float lam = geo::kPi2 - ang;
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh || j.uv) geo::sky_uv(j.f->central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+            const size_t o = (size_t)ly * j.width + px;
+            const uint32_t base = bh ? geo::kBlackRGBA : geo::sample_sky(fetch, j.sw, j.sh, j.opaque, U, V);
+            j.rgba[o] = geo::disk_shade(j.dk, k, dr, Uk, n, ang, base, dsample,
+                                        j.hits ? j.hits + o * (2u * geo::kDiskMaxCrossings) : nullptr);
+            if (j.mask) j.mask[o] = bh ? 1 : 0;
+            if (j.uv) {
+                j.uv[2 * o] = U;
+                j.uv[2 * o + 1] = V;
+            }
+            if (j.steps) j.steps[o] = n;
+            total += n;
+        }
+    }
+    return total;
+}
+
 // rows tid, tid + nthreads, ... of the job (interleaved: the frame's cost is
 // centre-heavy); returns the thread's executed RK4 steps
 unsigned long long run_rows(const CpuJob& j, unsigned tid, unsigned nthreads) {
+    if (j.disk) return run_rows_disk(j, tid, nthreads);
     if (j.mips) return run_rows_mips(j, tid, nthreads);
     unsigned long long total = 0;
     const float psi_k = j.f->psi_factor_and_position[0];
@@ -197,11 +253,14 @@ unsigned long long run_rows(const CpuJob& j, unsigned tid, unsigned nthreads) {
 
 }  // namespace
 
-extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
-                              uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
-                              uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
-                              uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
-                              unsigned long long* steps_total) {
+namespace {
+
+// disk: geo_render_cpu_disk's disk (scene->flags then carries GEO_FLAG_DISK), else null
+int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8, uint32_t sky_w,
+                    uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width, uint32_t height, uint32_t row0,
+                    uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                    float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, const geo_disk* disk,
+                    const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits) {
     if (!frame || !scene || !sky_rgba8 || !out_rgba8 || sky_w == 0 || sky_h == 0 || width == 0 || height == 0 ||
         row_step == 0 || width > (1u << 20) || height > (1u << 20))
         return GEO_EINVAL;
@@ -212,11 +271,25 @@ extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, co
     if ((uint64_t)row0 + (uint64_t)(nrows - 1) * row_step >= height) return GEO_EINVAL;
     if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
         return GEO_EINVAL;
-    if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64)) != 0)
+    if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
+                          (disk ? GEO_FLAG_DISK : 0u))) != 0)
         return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
         return GEO_EINVAL;
+    if (disk) {
+        // geo_render_rows' GEO_FLAG_DISK rules and geo_set_disk's (geo.h)
+        if ((scene->flags & GEO_FLAG_DISK) == 0 || scene->mode != GEO_MODE_DIRECT ||
+            (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0)
+            return GEO_EINVAL;
+        if (!disk_rgba8 || disk_w == 0 || disk_h == 0 || disk_w > (1u << 20) || disk_h > (1u << 20) ||
+            ((uint64_t)disk_w + 2u) * ((uint64_t)disk_h + 2u) * 4u >= (1ull << 31))
+            return GEO_EINVAL;
+        if (!(disk->r_in > 0.0f) || !(disk->r_in < disk->r_out) || !(disk->r_out < 3.0e38f)) return GEO_EINVAL;
+        if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < disk->r_in)) ||
+            !(disk->r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
+            return GEO_EINVAL;
+    }
     if (scene->mode == GEO_MODE_FAN && (!fan || n_fan < 2)) return GEO_EINVAL;
     if (scene->mode != GEO_MODE_FAN &&
         (!(scene->step > 0.0f) || !(scene->r_obs > 0.0f) || !(scene->sphere_r > 0.0f) || !(scene->rs >= 0.0f)))
@@ -258,6 +331,19 @@ extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, co
     j.steps = out_steps;
     j.ring = ring_flag && scene->rs > 0.0f && scene->r_obs > scene->rs;
     if (j.ring) j.band = geo::band_consts(*frame, *scene, width, height);
+    j.disk = disk != nullptr;
+    j.dtex = nullptr;
+    j.dw = disk_w;
+    j.dh = disk_h;
+    j.hits = out_hits;
+    std::vector<uint32_t> dtex;
+    if (disk) {
+        if (!geo::disk_consts(frame->central_to_uv, disk->normal, disk->axis, disk->r_in, disk->r_out, j.k, &j.dk))
+            return GEO_EINVAL;
+        dtex.resize((size_t)disk_w * disk_h);
+        std::memcpy(dtex.data(), disk_rgba8, dtex.size() * 4u);
+        j.dtex = dtex.data();
+    }
     // GEO_FLAG_MIPS: the chain geo_set_sky builds (geo::mip_down, level by level)
     j.mips = (scene->flags & GEO_FLAG_MIPS) != 0;
     std::vector<uint32_t> chain[geo::kSkyMipLevels];
@@ -287,4 +373,28 @@ extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, co
     for (unsigned long long p : part) total += p;
     if (steps_total) *steps_total = total;
     return GEO_OK;
+}
+
+}  // namespace
+
+extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                              uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
+                              uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                              uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                              unsigned long long* steps_total) {
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, nullptr, nullptr, 0, 0,
+                           nullptr);
+}
+
+extern "C" int geo_render_cpu_disk(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                   uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
+                                   uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                                   uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                                   unsigned long long* steps_total, const geo_disk* disk, const uint8_t* disk_rgba8,
+                                   uint32_t disk_w, uint32_t disk_h, float* out_hits) {
+    if (!disk) return GEO_EINVAL;
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits);
 }

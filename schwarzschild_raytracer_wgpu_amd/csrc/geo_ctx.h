@@ -6,6 +6,8 @@
 
 #include <stdint.h>
 
+#include "../../include/geo/geo.h"
+
 struct geo_ctx {
     int device;
     int num_cus;
@@ -101,6 +103,13 @@ struct geo_ctx {
     unsigned long long costs_recorded, orders_adopted;  // geo_dispatch_stats
     // geo_time_next_render: events for the next render's kernel dispatch
     hipEvent_t time_start, time_stop;
+    // GEO_FLAG_DISK (geo_set_disk): the disk, its padded texture (geo::pad_sky)
+    // and the hit buffer of geo_disk_hits_next_render (the next render's alone)
+    bool disk_set;
+    geo_disk disk;
+    uint32_t* disk_tex;
+    uint32_t disk_w, disk_h, disk_bytes;
+    float* hits_next;
 #if defined(GEO_WAVE_LOG)
     unsigned long long* wave_log;  // diagnostic build only (geo_debug_set_wave_log)
 #endif

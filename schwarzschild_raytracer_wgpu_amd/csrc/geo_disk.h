@@ -1,0 +1,325 @@
+// geo_disk.h — GEO_FLAG_DISK: a ray-traced thin accretion disk on the
+// per-pixel path (a build extension, not in the reference).
+//
+// A ray lies in one plane through the centre, and the disk plane (through the
+// centre, unit normal n in the sky texture's frame) cuts that plane along a
+// line: the ray meets the disk plane at the traveled angles a_k = a_0 + k pi,
+// known before the first RK4 step.  A disk hit is the integrator's u at a_k
+// (one partial RK4 step from the grid node below a_k) inside the annulus.
+//
+// Shared by the render kernel (geo_render.hip) and the CPU path
+// (cpu_render.cpp, geo_render_cpu_disk): the same f32 operation sequence, so
+// the two agree bit for bit.  The f32 specification:
+//   * (cos phi, sin phi) = (c2x, c2y) * rcpf_(rho)  ((1, 0) for rho = 0)
+//   * A = fma(N_x, cos phi, N_y sin phi), B = N_z, N = M2^T n (host, f64,
+//     rounded once); s = +1 if B < 0 or (B = 0 and A < 0), else -1;
+//     (y, x) = (-s B, s A), so y >= 0;  a_0 = 2 pi atan2_turns_(y, x) in
+//     (0, pi];  H = sqrtf_(fma(y, y, x x)), (sin a_0, cos a_0) = (y, x) rcpf_(H);
+//     H = 0 (or NaN): no crossing
+//   * a_k = fma(k, pi, a_0);  node j_k = floor(min(a_k * (1/step), 2^24)),
+//     partial step d_k = fma(-j_k, step, a_k) (may fall an ulp outside
+//     [0, step]: the RK4 map is evaluated there all the same)
+//   * U(a_k) = rk4_step from the main loop's state at node j_k with step d_k
+//     (half steps and squares formed as newton_angle forms them)
+//   * crossing k is a hit when j_k < steps (the main loop executed the step
+//     that starts at node j_k), a_k < the returned traveled angle (kNoValue
+//     = 15 > a_2 when the ray never crosses the sphere) and
+//     u_lo <= U <= u_hi, (u_lo, u_hi) = (scale / r_out, scale / r_in)
+//   * r = scale * rcpf_(U);  Vd = med3((r - r_in) * (1 / (r_out - r_in)), 0, 1);
+//     Ud = med3(atan2_turns_(Y, X), 0, 1) with (X, Y) the hit direction's
+//     components along the disk basis: X = fma(sin a_k, fma(Ex_x, cos phi,
+//     Ex_y sin phi), cos a_k Ex_z), E = M2^T e (host, f64, rounded once),
+//     (sin a_k, cos a_k) = (-1)^k (sin a_0, cos a_0).
+// A ray the reference's pre-filters or radial cases end before the loop
+// (geodesic_init: an observer inside the photon sphere) integrates nothing
+// and draws no disk.
+#pragma once
+
+#include <stdint.h>
+
+#include "geo_pixel.h"
+
+namespace geo {
+
+constexpr int kDiskMaxCrossings = 3;  // GEO_DISK_MAX_CROSSINGS
+constexpr float kTwoPi = 6.28318530717958647692f;
+constexpr float kDiskMaxNode = 16777216.0f;  // 2^24 >= max_steps: never a hit
+
+// Frame-uniform disk constants (host, f64, each rounded once to f32).
+struct DiskConsts {
+    float N[3];           // M2^T n
+    float ex[3], ey[3];   // M2^T e_x, M2^T e_y
+    float r_in, r_out;
+    float inv_dr;         // 1 / (r_out - r_in) (f32 divide)
+    float u_lo, u_hi;     // scale / r_out, scale / r_in (f32 divides)
+    float inv_step;       // 1 / step (f32 divide)
+};
+
+// m2: central_to_uv (column-major 4 x 4); n, axis: the disk's normal and the
+// direction of azimuth 0, in the sky texture's frame.  False for a zero normal
+// or an axis parallel to it.
+GEO_HD bool disk_consts(const float* m2, const float* normal, const float* axis, float r_in, float r_out,
+                        const PixelConsts& k, DiskConsts* out) {
+    double n[3] = {(double)normal[0], (double)normal[1], (double)normal[2]};
+    const double nl = __builtin_sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!(nl > 0.0) || !(nl < 1e300)) return false;
+    for (int i = 0; i < 3; ++i) n[i] /= nl;
+    const double an = (double)axis[0] * n[0] + (double)axis[1] * n[1] + (double)axis[2] * n[2];
+    double e[3];
+    for (int i = 0; i < 3; ++i) e[i] = (double)axis[i] - an * n[i];
+    const double el = __builtin_sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    const double al = __builtin_sqrt((double)axis[0] * axis[0] + (double)axis[1] * axis[1] + (double)axis[2] * axis[2]);
+    if (!(el > 1e-12 * al) || !(el < 1e300)) return false;
+    for (int i = 0; i < 3; ++i) e[i] /= el;
+    const double f[3] = {n[1] * e[2] - n[2] * e[1], n[2] * e[0] - n[0] * e[2], n[0] * e[1] - n[1] * e[0]};
+    for (int i = 0; i < 3; ++i) {
+        // (M2^T v)_i = column i of M2 . v
+        const double c0 = (double)m2[4 * i], c1 = (double)m2[4 * i + 1], c2 = (double)m2[4 * i + 2];
+        out->N[i] = (float)(c0 * n[0] + c1 * n[1] + c2 * n[2]);
+        out->ex[i] = (float)(c0 * e[0] + c1 * e[1] + c2 * e[2]);
+        out->ey[i] = (float)(c0 * f[0] + c1 * f[1] + c2 * f[2]);
+    }
+    out->r_in = r_in;
+    out->r_out = r_out;
+    out->inv_dr = 1.0f / (r_out - r_in);
+    out->u_lo = k.scale / r_out;
+    out->u_hi = k.scale / r_in;
+    out->inv_step = 1.0f / k.step;
+    return true;
+}
+
+// The crossings of one ray: angles, nodes and partial steps, known before the
+// integration.
+struct DiskRay {
+    float cphi, sphi;  // the ray plane's azimuth
+    float sa, ca;      // sin a_0, cos a_0
+    float ak[kDiskMaxCrossings];
+    uint32_t jn[kDiskMaxCrossings];  // 0xFFFFFFFF: no crossing
+    float dn[kDiskMaxCrossings];
+};
+
+GEO_HD void disk_ray(const DiskConsts& d, const PixelConsts& k, float c2x, float c2y, float rho, float rrho,
+                     DiskRay* r) {
+    float cphi = 1.0f, sphi = 0.0f;
+    if (rho > 0.0f) {
+        cphi = c2x * rrho;
+        sphi = c2y * rrho;
+    }
+    r->cphi = cphi;
+    r->sphi = sphi;
+    const float A = fmaf_(d.N[0], cphi, d.N[1] * sphi), B = d.N[2];
+    const float s = (B < 0.0f || (B == 0.0f && A < 0.0f)) ? 1.0f : -1.0f;
+    const float y = -s * B, x = s * A;
+    const float H = sqrtf_(fmaf_(y, y, x * x));
+    const bool crosses = H > 0.0f;
+    const float rH = rcpf_(H);
+    r->sa = y * rH;
+    r->ca = x * rH;
+    const float a0 = kTwoPi * atan2_turns_(y, x);
+#pragma unroll
+    for (int c = 0; c < kDiskMaxCrossings; ++c) {
+        const float a = fmaf_((float)c, kPi, a0);
+        const float jf = __builtin_fminf(a * d.inv_step, kDiskMaxNode);
+        const uint32_t j = crosses ? (uint32_t)floor_i32_(jf) : 0xFFFFFFFFu;
+        r->ak[c] = a;
+        r->jn[c] = j;
+        r->dn[c] = fmaf_(-(float)j, k.step, a);
+    }
+}
+
+// U at the end of a partial RK4 step of length dl from (pu, pb).
+template <int KIND>
+GEO_HD float disk_partial_(float pu, float pb, float dl) {
+    const float d2 = dl * dl;
+    const float d6 = dl * kSixth;
+    float wu, wub;
+    rk4_step<KIND>(pu, pb, dl, dl * 0.5f, d2 * 0.25f, d2 * 0.5f, d6, dl * d6, &wu, &wub);
+    return wu;
+}
+
+// geodesic_angle_v with the disk probes: the same traveled angle and step
+// count, and in Uk[c] the integrator's U at crossing c for every crossing
+// whose node the loop reached before the lane's stopping group ended (0
+// otherwise; disk_hit decides which of them count).
+//
+// The loop keeps geodesic_angle_v's groups of kGroup steps, its exact group
+// stop tests (group_stop_) and its finish (geodesic_finish), on one register
+// set in place of the pair loop's two: a probe reads the state at a node
+// inside the group, which the pair loop's alternating sets do not keep
+// addressable by node.  Per group the disk costs one compare (the lane's next
+// node against the group's end) and the rarely taken arm that does the
+// partial step.
+template <int KIND>
+GEO_HD float geodesic_angle_disk(const PixelConsts& k, float st, float ct, float rct, const DiskRay& dr,
+                                 uint32_t* steps, float (&Uk)[kDiskMaxCrossings]) {
+    constexpr int G = kGroup;
+    *steps = 0;
+#pragma unroll
+    for (int c = 0; c < kDiskMaxCrossings; ++c) Uk[c] = 0.0f;
+    float U, UB, early;
+    if (!geodesic_init<KIND>(k, st, ct, rct, &early, &U, &UB)) return early;
+    float h = k.step, hh = k.hh, hh2 = k.hh2, hhh = k.hhh, h6 = k.h6, h2_6 = k.h2_6;
+    StopTest<KIND> stop_at(k);
+    GEO_OPAQUE(h);
+    GEO_OPAQUE(hh);
+    GEO_OPAQUE(hh2);
+    GEO_OPAQUE(hhh);
+    GEO_OPAQUE(h6);
+    GEO_OPAQUE(h2_6);
+    GEO_OPAQUE(stop_at.lo);
+    GEO_OPAQUE(stop_at.hi);
+    const uint32_t ms = k.max_steps;
+    const uint32_t all = (ms / (uint32_t)G) * (uint32_t)G;
+    // the lane's next crossing: slot kc at node jt with partial step dt
+    uint32_t kc = 0, jt = dr.jn[0];
+    float dt = dr.dn[0];
+    // (three scalars and selects: a store at a per-lane slot index would put
+    // the array in scratch memory)
+    float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f;
+    auto probe = [&](float pu, float pb) {
+        const float v = disk_partial_<KIND>(pu, pb, dt);
+        u0 = kc == 0u ? v : u0;
+        u1 = kc == 1u ? v : u1;
+        u2 = kc == 2u ? v : u2;
+        ++kc;
+        jt = kc == 1u ? dr.jn[1] : (kc == 2u ? dr.jn[2] : 0xFFFFFFFFu);
+        dt = kc == 1u ? dr.dn[1] : dr.dn[2];
+    };
+    float su_[G + 1], sb_[G + 1];
+#pragma unroll
+    for (int j = 0; j <= G; ++j) {
+        GEO_UNSET(su_[j]);
+        GEO_UNSET(sb_[j]);
+    }
+    float cu = U, cb = UB;
+    // The loop's exit is wave-uniform, as in run_groups_pp and the adaptive
+    // loop: the lanes still integrating are the scalar mask `live`; a lane
+    // that stops records its stopping group's states in a rarely taken block,
+    // leaves `live` and keeps stepping harmlessly (its registers are no longer
+    // read).  One exit edge: an empty `live` ends the count.
+    uint64_t live = ballot_(true);
+    uint32_t it = all, n = 0;
+    uint32_t rem = ms / (uint32_t)G;
+    while (rem != 0) {
+        float ou[G], ob[G];
+        group_steps_<G, KIND>(cu, cb, h, hh, hh2, hhh, h6, h2_6, ou, ob);
+        const uint64_t due = ballot_(jt < n + (uint32_t)G) & live;
+        if (due != 0) {
+            if (in_ballot_(due)) {
+                GEO_RARE();
+                do {
+                    const uint32_t idx = jt - n;  // 0 .. G-1: the group's start state, or ou[idx - 1]
+                    float pu = cu, pb = cb;
+#pragma unroll
+                    for (int j = 1; j < G; ++j) {
+                        pu = idx == (uint32_t)j ? ou[j - 1] : pu;
+                        pb = idx == (uint32_t)j ? ob[j - 1] : pb;
+                    }
+                    probe(pu, pb);
+                } while (jt < n + (uint32_t)G);
+            }
+        }
+        uint64_t hit;
+        if constexpr (KIND == kCurvedIn)
+            hit = group_stop_<G, KIND, kTestEach>(stop_at, ou, ob);
+        else if (stop_at.above0)  // frame-uniform
+            hit = group_stop_<G, KIND, kTestLow>(stop_at, ou, ob);
+        else
+            hit = group_stop_<G, KIND, kTestBoth>(stop_at, ou, ob);
+        hit &= live;
+        --rem;
+        if (hit != 0) {
+            if (in_ballot_(hit)) {
+                GEO_RARE();
+                su_[0] = cu;
+                sb_[0] = cb;
+#pragma unroll
+                for (int j = 0; j < G; ++j) {
+                    su_[j + 1] = ou[j];
+                    sb_[j + 1] = ob[j];
+                }
+                it = n;
+            }
+            live &= ~hit;
+            rem = live == 0 ? 0u : rem;
+        }
+        cu = ou[G - 1];
+        cb = ob[G - 1];
+        n += (uint32_t)G;
+    }
+    const bool stopped = it != all;
+    n = it;
+    if (!stopped) {
+        // the budget's tail of fewer than G steps (geodesic_finish replays
+        // it for the angle): the probes at its nodes
+#pragma unroll
+        for (int j = 0; j <= G; ++j) {
+            su_[j] = cu;
+            sb_[j] = cb;
+        }
+        float tu = cu, tb = cb;
+        for (uint32_t r = n; r < ms; ++r) {
+            while (jt == r) probe(tu, tb);
+            float nu, nub;
+            rk4_step<KIND>(tu, tb, k.step, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &nu, &nub);
+            if (stop_at(nu, nub)) break;
+            tu = nu;
+            tb = nub;
+        }
+    }
+    Uk[0] = u0;
+    Uk[1] = u1;
+    Uk[2] = u2;
+    return geodesic_finish<G, KIND>(k, stop_at, n, su_, sb_, steps);
+}
+
+// Crossing c of the ray: a hit?  Then its radius and disk texture coordinates.
+GEO_HD bool disk_hit(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr, int c, float Uc, uint32_t steps,
+                     float angle, float* r, float* Ud, float* Vd) {
+    const bool hit = (dr.jn[c] < steps) & (dr.ak[c] < angle) & (med3_(Uc, d.u_lo, d.u_hi) == Uc);
+    if (!hit) return false;
+    const float rr = k.scale * rcpf_(Uc);
+    const float sg = (c & 1) ? -1.0f : 1.0f;
+    const float sa = sg * dr.sa, ca = sg * dr.ca;
+    const float X = fmaf_(sa, fmaf_(d.ex[0], dr.cphi, d.ex[1] * dr.sphi), ca * d.ex[2]);
+    const float Y = fmaf_(sa, fmaf_(d.ey[0], dr.cphi, d.ey[1] * dr.sphi), ca * d.ey[2]);
+    *r = rr;
+    *Ud = med3_(atan2_turns_(Y, X), 0.0f, 1.0f);
+    *Vd = med3_((rr - d.r_in) * d.inv_dr, 0.0f, 1.0f);
+    return true;
+}
+
+template <int S, typename Sample>
+GEO_HD uint32_t disk_shade_slot_(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr, float Us, uint32_t steps,
+                                 float angle, uint32_t c, const Sample& sample, float* hits) {
+    float r = 0.0f, Ud = 0.0f, Vd = 0.0f;
+    if (disk_hit(d, k, dr, S, Us, steps, angle, &r, &Ud, &Vd)) {
+        c = composite_(sample(Ud, Vd), c);
+    } else {
+        r = 0.0f;
+        Ud = 0.0f;
+    }
+    if (hits) {
+        hits[2 * S] = r;
+        hits[2 * S + 1] = Ud;
+    }
+    return c;
+}
+
+// The disk over a pixel's base colour (what the plain render writes): the
+// hits composited far to near with the 8-bit blend; hits (optional): the
+// pixel's 3 x (r, Ud) slots.  sample(Ud, Vd): the level-0 sample of the disk
+// texture (U wraps, V clamps).
+template <typename Sample>
+GEO_HD uint32_t disk_shade(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr,
+                           const float (&Uk)[kDiskMaxCrossings], uint32_t steps, float angle, uint32_t base,
+                           const Sample& sample, float* hits) {
+    static_assert(kDiskMaxCrossings == 3, "three slots, written out (constant indices: the arrays stay in registers)");
+    uint32_t c = base;
+    c = disk_shade_slot_<2>(d, k, dr, Uk[2], steps, angle, c, sample, hits);
+    c = disk_shade_slot_<1>(d, k, dr, Uk[1], steps, angle, c, sample, hits);
+    c = disk_shade_slot_<0>(d, k, dr, Uk[0], steps, angle, c, sample, hits);
+    return c;
+}
+
+}  // namespace geo

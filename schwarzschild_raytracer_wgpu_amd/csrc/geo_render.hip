@@ -28,6 +28,7 @@
 #include "../../include/geo/geo.h"
 #include "geo_ctx.h"
 #include "geo_band.h"
+#include "geo_disk.h"
 #include "geo_pixel.h"
 
 // Work decomposition (measured): 32 x 8-pixel workgroup tiles
@@ -721,6 +722,85 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
 #endif
 }
 
+// ---- GEO_FLAG_DISK: the thin accretion disk (geo_disk.h) ----------------
+// The disk render's own kernel, so that geo_render_kernel's instantiations
+// carry no new branch, argument or register: GEO_MODE_DIRECT, level-0
+// sampler, one frame, one wave per workgroup on the 1-D grid of the plain
+// direct-mode render (wave_blocks), the same tile mapping, step counting and
+// tile-cost recording.
+struct DiskArgs {
+    geo::DiskConsts k;
+    const uint32_t* tex;  // padded (geo::pad_sky): (tex_w + 2) x (tex_h + 2) texels
+    float tex_w256, tex_h256;
+    uint32_t tex_pitch_b, tex_bytes;
+    float* out_hits;  // optional: 3 x (r, U) per pixel
+};
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                             const DiskArgs d) {
+    const FrameK& f = fb.f[0];
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
+    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    uint32_t steps = 0;
+    if (px < a.width && ly < a.nrows && py < a.height) {
+        float c2x, c2y, c2z;
+        geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                               &c2x, &c2y, &c2z);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        geo::DiskRay dr;
+        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const size_t o = (size_t)ly * a.width + px;
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
+                                                                    kBufferRsrcWord3),
+                                  d.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
+        };
+        a.out_rgba[o] = geo::disk_shade(d.k, a.k, dr, Uk, steps, ang, base, dsample,
+                                        d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr);
+        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
+        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
+        if (a.out_steps) a.out_steps[o] = steps;
+    }
+    // (every lane of the wave is active again here, as in geo_render_kernel)
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost) {
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1226,6 +1306,7 @@ void geo_ctx_destroy(geo_ctx* c) {
     for (int i = 0; i < geo_ctx::kStepCallSets; ++i)
         if (c->step_set_rec[i]) (void)hipEventSynchronize(c->step_set_free[i]);
     if (c->sky) (void)hipFree(c->sky);
+    if (c->disk_tex) (void)hipFree(c->disk_tex);
     for (int b = 0; b < 2; ++b) {
         if (c->fan[b]) (void)hipFree(c->fan[b]);
         (void)hipEventDestroy(c->fan_written[b]);
@@ -1314,6 +1395,67 @@ int geo_set_sky(geo_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h) {
     const size_t bytes = (size_t)w * h * 4;
     for (size_t i = 3; i < bytes && opaque; i += 4) opaque = rgba8[i] == 255;
     c->sky_opaque = opaque;  // the means of opaque texels are opaque: every level
+    return GEO_OK;
+}
+
+int geo_clear_disk(geo_ctx* c) {
+    if (!c) return GEO_EINVAL;
+    DeviceGuard g(c->device);
+    if (!g.ok) return GEO_EHIP;
+    if (c->disk_tex) {
+        if (wait_renders(c) != GEO_OK) return GEO_EHIP;
+        (void)hipFree(c->disk_tex);
+    }
+    c->disk_tex = nullptr;
+    c->disk_set = false;
+    return GEO_OK;
+}
+
+int geo_set_disk(geo_ctx* c, const geo_disk* disk, const uint8_t* rgba8, uint32_t w, uint32_t h) {
+    if (!c || !disk || !rgba8 || w == 0 || h == 0 || w > (1u << 20) || h > (1u << 20)) return GEO_EINVAL;
+    const uint64_t total = ((uint64_t)w + 2u) * ((uint64_t)h + 2u) * 4u;  // padded, 32-bit buffer offsets
+    if (total >= (1ull << 31)) return GEO_EINVAL;
+    if (!(disk->r_in > 0.0f) || !(disk->r_in < disk->r_out) || !(disk->r_out < 3.0e38f)) return GEO_EINVAL;
+    {
+        // the normal and the axis, checked as every render will derive them
+        // (any frame: the identity stands in for central_to_uv)
+        const float id[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        geo::DiskConsts dk;
+        if (!geo::disk_consts(id, disk->normal, disk->axis, disk->r_in, disk->r_out,
+                              geo::make_consts(0.0f, 2.0f * disk->r_out, disk->r_out, 0.03125f, 1u), &dk))
+            return GEO_EINVAL;
+    }
+    DeviceGuard g(c->device);
+    if (!g.ok) return GEO_EHIP;
+    std::vector<uint32_t> pad(total / 4u);
+    geo::pad_sky(rgba8, w, h, pad.data());
+    // renders in flight may sample the current disk texture (geo_set_sky's rule)
+    if (wait_renders(c) != GEO_OK) return GEO_EHIP;
+    c->disk_set = false;
+    if (c->disk_tex && c->disk_bytes != (uint32_t)total) {
+        (void)hipFree(c->disk_tex);
+        c->disk_tex = nullptr;
+    }
+    if (!c->disk_tex && hipMalloc(&c->disk_tex, total) != hipSuccess) {
+        c->disk_tex = nullptr;
+        return GEO_ENOMEM;
+    }
+    if (hipMemcpy(c->disk_tex, pad.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(c->disk_tex);
+        c->disk_tex = nullptr;
+        return GEO_EHIP;
+    }
+    c->disk_bytes = (uint32_t)total;
+    c->disk_w = w;
+    c->disk_h = h;
+    c->disk = *disk;
+    c->disk_set = true;
+    return GEO_OK;
+}
+
+int geo_disk_hits_next_render(geo_ctx* c, float* out_hits) {
+    if (!c || !out_hits) return GEO_EINVAL;
+    c->hits_next = out_hits;
     return GEO_OK;
 }
 
@@ -1512,6 +1654,31 @@ static int launch_frames(const RenderArgs& a, const FrameK* fk, const geo::Pixel
     return launch_tiles<MODE, KIND, kMaxBatchFrames>(a, fb, nframes, false, tiles_x, tiles_y, s, done, t_start,
                                                      t_stop, band);
 }
+
+// A GEO_FLAG_DISK frame (geo_render_disk_kernel): launch_tiles' loop on the
+// wave-block grid.
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) <= 4096, "kernel arguments fit 4 KiB");
+template <int KIND>
+static int launch_disk(RenderArgs a, const FrameK& fk, const DiskArgs& d, uint32_t tiles_x, uint32_t tiles_y,
+                       hipStream_t s, hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop) {
+    FrameBatch<1> fb;
+    fb.f[0] = fk;
+    a.tiles_x = tiles_x;
+    const uint32_t max_ny = std::min(kMaxGridY, kMaxWaveBlockTiles / tiles_x);
+    for (uint32_t y0 = 0; y0 < tiles_y; y0 += max_ny) {
+        a.tile_y0 = y0;
+        const uint32_t ny = tiles_y - y0 < max_ny ? tiles_y - y0 : max_ny;
+        a.launch_tiles = tiles_x * ny;
+        const bool last = y0 + ny >= tiles_y;
+        hipEvent_t start = y0 == 0 ? t_start : nullptr;
+        hipEvent_t stop = last ? (t_stop ? t_stop : done) : nullptr;
+        hipExtLaunchKernelGGL((geo_render_disk_kernel<KIND>), dim3(wave_block_count(a.launch_tiles)), dim3(64), 0, s,
+                              start, stop, 0, a, fb, d);
+        if (hipGetLastError() != hipSuccess) return GEO_EHIP;
+    }
+    if (t_stop && hipEventRecord(done, s) != hipSuccess) return GEO_EHIP;
+    return GEO_OK;
+}
 }
 
 // The order buffers hold at least n tiles (both orders, the costs, the class
@@ -1551,7 +1718,10 @@ static int ensure_tiles(geo_ctx* c, uint32_t n) {
 // A render call refused before render_impl: the timing pair of
 // geo_time_next_render is dropped too (it belongs to that call alone).
 static int invalid_call(geo_ctx* c) {
-    if (c) c->time_start = c->time_stop = nullptr;
+    if (c) {
+        c->time_start = c->time_stop = nullptr;
+        c->hits_next = nullptr;
+    }
     return GEO_EINVAL;
 }
 
@@ -1560,7 +1730,7 @@ static int invalid_call(geo_ctx* c) {
 // scene_per_frame: `scene` points at nframes scenes, frame f's at scene[f]
 // (they may differ in r_obs only); otherwise one scene for every frame.
 static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, size_t out_frame_stride,
-                       const geo_scene* scene, bool scene_per_frame, uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                       const geo_scene* scene, bool scene_per_frame, bool allow_disk, uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
                        uint32_t band_rows, uint32_t band_stride, uint8_t* out_rgba8, uint8_t* out_mask,
                        float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, void* stream) {
     // geo_time_next_render's events belong to this render alone, on every
@@ -1568,9 +1738,18 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     // must not record the caller's pair)
     const hipEvent_t t_start = c->time_start, t_stop = c->time_stop;
     c->time_start = c->time_stop = nullptr;
+    // geo_disk_hits_next_render's buffer likewise
+    float* const out_hits = c->hits_next;
+    c->hits_next = nullptr;
     if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
         return GEO_EINVAL;
-    if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64)) != 0)
+    if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
+                          GEO_FLAG_DISK)) != 0)
+        return GEO_EINVAL;
+    // GEO_FLAG_DISK: the one-frame entry points, direct mode, DEFER_STEPS at most
+    const bool disk = (scene->flags & GEO_FLAG_DISK) != 0;
+    if (disk && (!allow_disk || scene->mode != GEO_MODE_DIRECT ||
+                 (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0))
         return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
@@ -1594,6 +1773,12 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     if (scene->mode != GEO_MODE_FAN &&
         (!(scene->step > 0.0f) || !(scene->r_obs > 0.0f) || !(scene->sphere_r > 0.0f) || !(scene->rs >= 0.0f)))
         return GEO_EINVAL;
+    if (disk) {
+        if (!c->disk_set) return GEO_ESTATE;
+        if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < c->disk.r_in)) ||
+            !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
+            return GEO_EINVAL;
+    }
     DeviceGuard g(c->device);
     if (!g.ok) return GEO_EHIP;
     RenderArgs a;
@@ -1694,7 +1879,7 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
         } else if (c->dispatch_mode == GEO_DISPATCH_LONGEST_FIRST) {
             // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost more)
             const uint32_t key[9] = {width, height, row0, nrows, band_rows, band_stride, scene->mode,
-                                     (mips ? 1u : 0u) | (ring ? 2u : 0u), tiles_x * tiles_y};
+                                     (mips ? 1u : 0u) | (ring ? 2u : 0u) | (disk ? 4u : 0u), tiles_x * tiles_y};
             if (!c->learn_valid || std::memcmp(key, c->learn_key, sizeof(key)) != 0) {
                 std::memcpy(c->learn_key, key, sizeof(key));
                 c->learn_valid = true;
@@ -1737,7 +1922,9 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     if (ring && nframes == 1) band_k = geo::band_consts(frames[0], *scene, width, height);
     const geo::BandConsts* band = ring ? &band_k : nullptr;
     int st;
-    if (scene->mode == GEO_MODE_FAN) {
+    if (disk) {
+        st = GEO_OK;  // launched below, after the plain paths
+    } else if (scene->mode == GEO_MODE_FAN) {
         // after the solve that wrote the buffer (geo_ctx: on the solve's own
         // stream by stream order, with no event work: the reader is its
         // slot's bit); on another stream this render then joins the buffer's
@@ -1770,6 +1957,25 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
             case geo::kCurvedOut: st = launch_frames<GEO_MODE_DIRECT, geo::kCurvedOut>(a, fk, pk, nframes, mips, tiles_x, tiles_y, s, done, t_start, t_stop, band); break;
             case geo::kCurvedIn: st = launch_frames<GEO_MODE_DIRECT, geo::kCurvedIn>(a, fk, pk, nframes, mips, tiles_x, tiles_y, s, done, t_start, t_stop, band); break;
             default: st = launch_frames<GEO_MODE_DIRECT, geo::kFlat>(a, fk, pk, nframes, mips, tiles_x, tiles_y, s, done, t_start, t_stop);
+        }
+    }
+    // (the disk launch last, so that its kernels are instantiated, and laid out
+    // in the code object, after every kernel of the plain paths)
+    if (disk) {
+        DiskArgs d;
+        if (!geo::disk_consts(frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out, a.k,
+                              &d.k))
+            return GEO_EINVAL;
+        d.tex = c->disk_tex;
+        d.tex_w256 = (float)c->disk_w * 256.0f;
+        d.tex_h256 = (float)c->disk_h * 256.0f;
+        d.tex_pitch_b = (c->disk_w + 2u) * 4u;
+        d.tex_bytes = c->disk_bytes;
+        d.out_hits = out_hits;
+        switch (geo::geodesic_kind(a.k)) {
+            case geo::kCurvedOut: st = launch_disk<geo::kCurvedOut>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop); break;
+            case geo::kCurvedIn: st = launch_disk<geo::kCurvedIn>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop); break;
+            default: st = launch_disk<geo::kFlat>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop);
         }
     }
     if (st) return st;
@@ -1998,7 +2204,7 @@ int geo_render_rows(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, 
     if ((uint64_t)row0 + nrows > height || width > (1u << 20) || height > (1u << 20))
         return invalid_call(c);
     // one band covering every row (2^21 >= nrows)
-    return render_impl(c, frame, 1, 0, scene, false, width, height, row0, nrows, 1u << 21, 1u << 21, out_rgba8, out_mask,
+    return render_impl(c, frame, 1, 0, scene, false, true, width, height, row0, nrows, 1u << 21, 1u << 21, out_rgba8, out_mask,
                        out_uv, out_steps, steps_total, stream);
 }
 
@@ -2014,7 +2220,7 @@ int geo_render_bands(geo_ctx* c, const geo_frame* frame, const geo_scene* scene,
     const uint64_t last = first + (uint64_t)(nbands - 1) * band_step * band_rows;
     const uint64_t nrows = (uint64_t)nbands * band_rows;
     if (first >= height || last >= height || nrows > (1u << 20)) return invalid_call(c);
-    return render_impl(c, frame, 1, 0, scene, false, width, height, (uint32_t)first, (uint32_t)nrows,
+    return render_impl(c, frame, 1, 0, scene, false, true, width, height, (uint32_t)first, (uint32_t)nrows,
                        band_rows, band_step * band_rows, out_rgba8, out_mask, out_uv,
                        out_steps, steps_total, stream);
 }
@@ -2038,7 +2244,7 @@ int geo_render_band_set(geo_ctx* c, const geo_frame* frame, const geo_scene* sce
                         unsigned long long* steps_total, void* stream) {
     if (!c || !frame || !scene || !out_rgba8 || !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frame, 1, 0, scene, false, width, height, row0, nbands * band_rows, band_rows, row_stride,
+    return render_impl(c, frame, 1, 0, scene, false, true, width, height, row0, nbands * band_rows, band_rows, row_stride,
                        out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
 }
 
@@ -2049,7 +2255,7 @@ int geo_render_band_set_frames(geo_ctx* c, const geo_frame* frames, uint32_t nfr
     if (!c || !frames || !scene || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
         !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frames, nframes, out_frame_stride, scene, false, width, height, row0, nbands * band_rows,
+    return render_impl(c, frames, nframes, out_frame_stride, scene, false, false, width, height, row0, nbands * band_rows,
                        band_rows, row_stride, out_rgba8, nullptr, nullptr, nullptr, steps_total, stream);
 }
 
@@ -2060,7 +2266,7 @@ int geo_render_band_set_batch(geo_ctx* c, const geo_frame* frames, const geo_sce
     if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
         !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frames, nframes, out_frame_stride, scenes, true, width, height, row0, nbands * band_rows,
+    return render_impl(c, frames, nframes, out_frame_stride, scenes, true, false, width, height, row0, nbands * band_rows,
                        band_rows, row_stride, out_rgba8, nullptr, nullptr, nullptr, steps_total, stream);
 }
 

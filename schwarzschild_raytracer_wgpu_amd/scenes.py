@@ -81,3 +81,23 @@ def make_sky(kind: str = "equirect", size=(4096, 2048), seed: int = 0x5C4A) -> n
     sky[..., :3] = np.clip(rgb, 0, 255).astype(np.uint8)
     sky[..., 3] = 255
     return sky
+
+
+def make_disk_texture(size=(512, 64)) -> np.ndarray:
+    """(h, w, 4) uint8 disk texture for Context.set_disk: U (columns) is the
+    azimuth, V (rows) the radius from r_in to r_out.  A radial gradient (hot
+    white-yellow inside to dull red outside) with 16 azimuthal stripes; alpha
+    rises from 0 at both rims to 255 (a smooth window), so the rims fade out."""
+    w, h = size
+    u = (np.arange(w, dtype=np.float64) + 0.5) / w
+    v = (np.arange(h, dtype=np.float64) + 0.5) / h
+    stripe = 0.75 + 0.25 * np.cos(2.0 * math.pi * 16.0 * u)[None, :]
+    t = v[:, None]
+    rgb = np.stack([255.0 * (1.0 - 0.25 * t) * stripe, 230.0 * (1.0 - 0.7 * t) * stripe,
+                    160.0 * (1.0 - t) ** 2 * stripe], axis=-1)
+    tr = (np.arange(h, dtype=np.float64) / max(h - 1, 1))[:, None]  # 0 and 1 on the rim rows (V clamps to them)
+    alpha = np.clip(np.minimum(tr, 1.0 - tr) * 8.0, 0.0, 1.0) * np.ones((1, w))
+    tex = np.empty((h, w, 4), dtype=np.uint8)
+    tex[..., :3] = np.clip(np.rint(rgb), 0, 255).astype(np.uint8)
+    tex[..., 3] = np.clip(np.rint(255.0 * alpha), 0, 255).astype(np.uint8)
+    return tex

@@ -1,0 +1,206 @@
+"""An independent f64 answer for GEO_FLAG_DISK (the thin accretion disk).
+
+numpy, f64, no code shared with csrc/geo_disk.h:
+
+* the camera of shader.wgsl:60-75 restated (pixel centre NDC, FOV column,
+  display_to_movement, the aberration sin(l') = (s - k)/(1 - s k) as the
+  boost along z, movement_to_central); its angle to the black hole equals
+  oracle.render_f64's `theta` to ~4e-15 (test_disk_cpu checks 1e-12);
+* the ray in its plane: u0 = 1/r, u0' = (E/r) tan(theta), E = sqrt(1 - rs/r);
+* RK4 of the Binet equation u'' = -u + (3 rs/2) u^2 at step/8, with a partial
+  RK4 step from the fine node below each crossing angle a_k = a_0 + k pi;
+* the hit rule of include/geo/geo.h: crossing k (k < 3) is a hit when a_k lies
+  within the angle the main loop integrates (before the ray leaves the sky
+  sphere, u <= 1/sphere_r; before the horizon, u > 1/rs with u' > 0; before
+  the budget max_steps * step) and r_in <= 1/u(a_k) <= r_out.
+
+It assumes an observer inside the sky sphere and outside the photon sphere
+(r_obs > 3 rs/2, or rs = 0), where none of the reference's pre-filters
+(sphere_ray_tracer.rs:106-119) ends a ray before the loop.
+
+Tolerances (the scheme of f64_bar.py's K_AMP and A_DIR): the CPU path
+(geo_render_cpu_disk, bit-equal to the kernel) was measured against this
+module on a calibration set that is none of the test poses -- the disk 3..9
+(normal (0.2, 0.1, 1)) seen from (9, 2, 4) and the disk 1.6..2.2 seen from
+(3.1, 0.4, 0.9), each under five cameras (phi, theta) offsets (0, 0),
+(0.25, 0.1), (-0.3, 0.05), (0.1, -0.2), (-0.15, 0.15) from the direction to
+the centre, 96 x 54, fov pi/2, every pixel with |b/b_c - 1| >= 0.02, every
+slot hit on both sides:
+
+    max relative radius error   2.46e-5  (CAL_R)
+    max azimuth error (turns)   1.45e-7  (CAL_AZ)
+
+each multiplied by 4 (a finite calibration set) and rounded up to a power of
+two.  tests/test_disk_cpu.py::test_calibration_record re-measures them and
+checks the constants against the rule.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+CAL_R = 2.5e-5    # measured maximum 2.46e-5, relative radius (calibration set above)
+CAL_AZ = 1.5e-7   # measured maximum 1.45e-7, azimuth in turns
+TOL_R = 2.0 ** -13   # 1.22e-4: 4 * CAL_R = 1.0e-4 rounded up to a power of two
+TOL_AZ = 2.0 ** -20  # 9.5e-7: 4 * CAL_AZ = 6.0e-7 rounded up to a power of two
+BAND_X = 0.02     # |b/b_c - 1| below which a pixel is left to the bit-equality tests
+MAX_CROSSINGS = 3
+
+CAL_DISKS = [((9.0, 2.0, 4.0), 3.0, 9.0, (0.2, 0.1, 1.0)), ((3.1, 0.4, 0.9), 1.6, 2.2, (0.2, 0.1, 1.0))]
+CAL_CAMS = [(0.0, 0.0), (0.25, 0.1), (-0.3, 0.05), (0.1, -0.2), (-0.15, 0.15)]
+
+
+def tol_rule(measured: float) -> float:
+    """4 x the measured maximum, rounded up to a power of two."""
+    return 2.0 ** math.ceil(math.log2(4.0 * measured))
+
+
+def _m3(m16):
+    """3 x 3 part of a column-major 4 x 4 (f32 values, f64 arithmetic)."""
+    a = np.array([float(v) for v in m16], dtype=np.float64).reshape(4, 4).T
+    return a[:3, :3], a
+
+
+def camera(frame, width, height):
+    """Per pixel, in f64: the unit direction c2 (h, w, 3) in the black-hole-
+    central frame (shader.wgsl:60-75)."""
+    m0_3, m0 = _m3(frame.display_to_movement)
+    m1_3, _ = _m3(frame.movement_to_central)
+    k = float(frame.psi_factor_and_position[0])
+    px = np.arange(width, dtype=np.float64)[None, :]
+    py = np.arange(height, dtype=np.float64)[:, None]
+    nx = (2.0 * px + 1.0 - width) / width + 0.0 * py
+    ny = (height - 2.0 * py - 1.0) / height + 0.0 * px
+    # column 3 of display_to_movement carries the FOV scale (observer.rs:253-254)
+    v = np.stack([-ny * m0[0, 3], -nx * m0[1, 3], np.full_like(nx, m0[2, 3])], axis=-1)
+    d = v @ m0_3.T
+    L = np.linalg.norm(d, axis=-1)
+    den = L - k * d[..., 2]
+    e = np.stack([d[..., 0] * math.sqrt(1.0 - k * k) / den, d[..., 1] * math.sqrt(1.0 - k * k) / den,
+                  (d[..., 2] - k * L) / den], axis=-1)
+    return e @ m1_3.T
+
+
+def observer_world(frame, r_obs):
+    m2, _ = _m3(frame.central_to_uv)
+    return r_obs * (m2 @ np.array([0.0, 0.0, 1.0]))
+
+
+def disk_basis(normal, axis):
+    n = np.asarray(normal, dtype=np.float64)
+    n = n / np.linalg.norm(n)
+    a = np.asarray(axis, dtype=np.float64)
+    ex = a - a.dot(n) * n
+    ex = ex / np.linalg.norm(ex)
+    return n, ex, np.cross(n, ex)
+
+
+def _f(u, c):
+    return -u + c * u * u
+
+
+def _rk4(u, v, h, c):
+    """One RK4 step of (u, v)' = (v, f(u)), elementwise step h."""
+    k1u, k1v = v, _f(u, c)
+    k2u, k2v = v + 0.5 * h * k1v, _f(u + 0.5 * h * k1u, c)
+    k3u, k3v = v + 0.5 * h * k2v, _f(u + 0.5 * h * k2u, c)
+    k4u, k4v = v + h * k3v, _f(u + h * k3u, c)
+    return u + h / 6.0 * (k1u + 2 * k2u + 2 * k3u + k4u), v + h / 6.0 * (k1v + 2 * k2v + 2 * k3v + k4v)
+
+
+def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis=(1.0, 0.0, 0.0), sub=8):
+    """dict: hit (h, w, 3) bool, r, az (h, w, 3) f64 (radius and azimuth in
+    turns in [0, 1) of each crossing, nan where the ray never got there), x
+    (h, w) = |b/b_c - 1| (inf for rs = 0), theta (h, w)."""
+    rs, R, r0 = float(scene.rs), float(scene.sphere_r), float(scene.r_obs)
+    step, budget = float(scene.step), int(scene.max_steps)
+    c2 = camera(frame, width, height)
+    rho = np.hypot(c2[..., 0], c2[..., 1])
+    st = np.clip(c2[..., 2], -1.0, 1.0)
+    theta = np.arctan2(st, rho)
+    cphi, sphi = c2[..., 0] / rho, c2[..., 1] / rho
+    m2, _ = _m3(frame.central_to_uv)
+    n, ex, ey = disk_basis(normal, axis)
+    N, Ex, Ey = m2.T @ n, m2.T @ ex, m2.T @ ey
+    A = N[0] * cphi + N[1] * sphi
+    B = N[2]
+    a0 = np.mod(np.arctan2(-B, A), math.pi)
+    a0 = np.where(a0 <= 0.0, math.pi, a0)  # in (0, pi]
+    E = math.sqrt(1.0 - rs / r0) if rs > 0.0 else 1.0
+    u = np.full(rho.shape, 1.0 / r0)
+    v = (E / r0) * st / rho
+    c = 1.5 * rs
+    su, hu = 1.0 / R, (1.0 / rs if rs > 0.0 else math.inf)
+    h = step / sub
+    ak = a0[..., None] + math.pi * np.arange(MAX_CROSSINGS)[None, None, :]
+    t_end = min(float(ak.max()) + step, budget * step)
+    nsub = int(math.ceil(t_end / h))
+    alive = np.ones(rho.shape, dtype=bool)
+    uk = np.full(ak.shape, np.nan)
+    for i in range(nsub):
+        t0, t1 = i * h, (i + 1) * h
+        for k in range(MAX_CROSSINGS):
+            m = alive & (ak[..., k] >= t0) & (ak[..., k] < t1) & (ak[..., k] < budget * step)
+            if m.any():
+                uu, _ = _rk4(u[m], v[m], ak[..., k][m] - t0, c)
+                # the ray may leave the sphere or pass the horizon inside this
+                # substep before a_k: then u(a_k) itself shows it (outside the annulus)
+                uk[..., k][m] = uu
+        nu, nv = _rk4(u, v, h, c)
+        gone = (nu <= su) | ((nu > hu) & (nv > 0.0)) | ~np.isfinite(nu)
+        u = np.where(alive, nu, u)
+        v = np.where(alive, nv, v)
+        alive &= ~gone
+        if not alive.any():
+            break
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = 1.0 / uk
+    hit = np.isfinite(r) & (r >= r_in) & (r <= r_out)
+    sa, ca = np.sin(ak), np.cos(ak)
+    X = sa * (Ex[0] * cphi + Ex[1] * sphi)[..., None] + ca * Ex[2]
+    Y = sa * (Ey[0] * cphi + Ey[1] * sphi)[..., None] + ca * Ey[2]
+    az = np.mod(np.arctan2(Y, X) / (2.0 * math.pi), 1.0)
+    if rs > 0.0 and r0 > rs:
+        x = np.abs(r0 * np.cos(theta) / E / (1.5 * math.sqrt(3.0) * rs) - 1.0)
+    else:
+        x = np.full(theta.shape, np.inf)
+    return dict(hit=hit, r=r, az=az, x=x, theta=theta)
+
+
+def az_err(a, b):
+    d = np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))
+    return np.minimum(d, 1.0 - d)
+
+
+def compare(cpu_hits, ref, r_in, r_out, slots=(0, 1, 2), use_band=True):
+    """cpu_hits: (h, w, 3, 2) f32 (r, U) slots of the CPU path or the kernel.
+    Returns per-slot statistics and the worst errors; raises nothing."""
+    out = {}
+    keep = (ref["x"] >= BAND_X) if use_band else np.ones(ref["x"].shape, dtype=bool)
+    out["excluded_share"] = 1.0 - float(keep.mean())
+    worst_r = worst_az = 0.0
+    bad_edges = 0
+    for k in slots:
+        got = cpu_hits[..., k, 0] > 0.0
+        want = ref["hit"][..., k]
+        both = got & want & keep
+        if both.any():
+            er = np.abs(cpu_hits[..., k, 0][both].astype(np.float64) / ref["r"][..., k][both] - 1.0)
+            ea = az_err(cpu_hits[..., k, 1][both], ref["az"][..., k][both])
+            worst_r = max(worst_r, float(er.max()))
+            worst_az = max(worst_az, float(ea.max()))
+        dis = (got != want) & keep
+        rr = ref["r"][..., k]
+        with np.errstate(invalid="ignore"):
+            near_edge = (np.abs(rr / r_in - 1.0) <= TOL_R) | (np.abs(rr / r_out - 1.0) <= TOL_R)
+        bad_edges += int((dis & ~near_edge).sum())
+        out[f"total{k}"] = int(got.sum())
+        out[f"ref_total{k}"] = int(want.sum())
+        out[f"hits{k}"] = int((got & keep).sum())
+        out[f"ref_hits{k}"] = int((want & keep).sum())
+        out[f"disagree{k}"] = int(dis.sum())
+    out["max_rel_r"] = worst_r
+    out["max_az"] = worst_az
+    out["disagree_off_edge"] = bad_edges
+    return out

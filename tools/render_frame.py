@@ -6,6 +6,12 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.png [--width 1920 --height 1080]
         [--sky eso0932a.jpg --planet world_8k.png --clouds transparent_clouds.png]
         [--frames 60 --orbit 3.2] [--mipmaps] [--fan]
+  python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
+
+--disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
+the sky sphere alone plus the textured disk with its secondary and third
+images) instead of the reference's scene; --cpu renders it with the CPU path
+(libgeo_cpu.so, the same bytes, no GPU needed).
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -20,6 +26,58 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def disk_frame(args):
+    """One GEO_FLAG_DISK frame: sky sphere 50, rs = 1, step pi/100, 2048 steps."""
+    import ctypes
+
+    import numpy as np
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib, imageio
+    from schwarzschild_raytracer_wgpu_amd.scenes import make_disk_texture, make_sky
+
+    w, h = args.width, args.height
+    obs = g.Observer(1.0, args.fov, w, h)
+    obs.set_position(*args.pos)
+    obs.set_camera(*args.camera)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(1.0, 50.0, obs.get_radial_position(), math.pi / 100, 2048, flags=_lib.GEO_FLAG_DISK)
+    sky = imageio.load_texture(args.sky) if args.sky else make_sky("equirect", (2048, 1024))
+    tex = make_disk_texture((1024, 128))
+    r_in, r_out = args.disk
+    if args.cpu:
+        lib = ctypes.CDLL(os.path.join(ROOT, "schwarzschild_raytracer_wgpu_amd", "libgeo_cpu.so"))
+        disk = _lib.GeoDisk(r_in, r_out, (ctypes.c_float * 3)(*args.disk_normal), (ctypes.c_float * 3)(1.0, 0.0, 0.0))
+        sky = np.ascontiguousarray(sky)
+        rgba = np.zeros((h, w, 4), np.uint8)
+        vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+        lib.geo_render_cpu_disk.restype = ctypes.c_int
+        lib.geo_render_cpu_disk.argtypes = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int, vp,
+                                            vp, vp, vp, vp, vp, vp, u32, u32, vp]
+        rc = lib.geo_render_cpu_disk(ctypes.addressof(frame), ctypes.addressof(scene), sky.ctypes.data, sky.shape[1],
+                                     sky.shape[0], None, 0, w, h, 0, h, 1, 0, rgba.ctypes.data, None, None, None, None,
+                                     ctypes.addressof(disk), tex.ctypes.data, tex.shape[1], tex.shape[0], None)
+        if rc != 0:
+            raise SystemExit(f"geo_render_cpu_disk: {rc}")
+    else:
+        import torch
+
+        ctx = g.Context(0)
+        ctx.set_sky(sky)
+        ctx.set_disk(tex, r_in, r_out, normal=args.disk_normal)
+        rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
+        ctx.render_rows(frame, scene, w, h, 0, h, rgba)
+    if args.out.endswith(".ppm"):
+        imageio.save_ppm(args.out, rgba, w, h)
+    elif args.out.endswith((".jpg", ".jpeg")):
+        from PIL import Image
+
+        Image.fromarray(imageio.frame_to_host(rgba, w, h)[..., :3].copy(), "RGB").save(args.out, quality=88)
+    else:
+        imageio.save_png(args.out, rgba, w, h)
+    print(f"wrote {args.out} ({w}x{h}, thin disk {r_in}..{r_out}, {'CPU path' if args.cpu else 'GPU'})")
 
 
 def main():
@@ -37,7 +95,16 @@ def main():
     p.add_argument("--fan", action="store_true",
                    help="the reference's display path: per-frame 400-node f64 ray fans and the fan lerp "
                         "(GEO_MODE_FAN) instead of a geodesic per pixel")
+    p.add_argument("--disk", type=float, nargs=2, metavar=("R_IN", "R_OUT"),
+                   help="the ray-traced thin disk (GEO_FLAG_DISK) over the sky sphere")
+    p.add_argument("--disk-normal", type=float, nargs=3, default=(0.0, 0.0, 1.0))
+    p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (geo_render_cpu_disk)")
+    p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
+    p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
+    p.add_argument("--fov", type=float, default=math.pi / 2, help="with --disk")
     args = p.parse_args()
+    if args.disk:
+        return disk_frame(args)
 
     import torch
 
