@@ -71,8 +71,11 @@ struct PixelConsts {
     // on the host (gfx9 has no scalar float compares, so the kernel would
     // evaluate them in VALU on every lane): StopTest's interval [stop_lo,
     // stop_hi] and stop_bits = above0 (U0 > SU) | (max_steps != 0 && u0 > 0) << 2
+    // | (the frame admits the end-state exit test, kTestEnd of group_stop_, for
+    // the lanes whose UB0 lies in [end_lo, end_hi]) << 3
     float stop_lo, stop_hi;
     uint32_t stop_bits;
+    float end_lo, end_hi;
     int kind;  // the frame's integration kind (geodesic_kind)
     // the integrator's scaled state U = scale*u (scale = 3 rs/2, or 1 for rs = 0)
     float scale, U0, SU, BD, HU;
@@ -131,6 +134,23 @@ GEO_HD bool lane_select_(LaneMask m, bool a, bool b) { return m ? a : b; }
 // general kCurvedIn test.
 constexpr float kHorizonStepMin = 0x1p-10f;
 constexpr float kHorizonStepMax = 0.5f;
+
+// Frames and lanes for which the end-state exit test (kTestEnd) equals the
+// exact one; the argument is at group_stop_.  Frame-uniform: the observer
+// inside the sphere, kCurvedOut or kFlat, a step in [kHorizonStepMin,
+// kEndStepMax], lo = SU+ in [kEndLoMin, kEndLoMax] (kFlat: no upper limit)
+// and U0 <= kEndUMax.  Per lane: -B <= UB0 <= kEndUbMax, where for kCurvedOut
+//   h (sqrt(B^2 + 1) + 2 h) <= kEndProd = 1/20
+// (the argument needs h W <= 1/5 for W = sqrt(B^2 + 1) + 2 h, the bound on
+// -U' of a descending state: a safety factor of 4), which has a solution
+// B >= 0 for h <= (sqrt(1.4) - 1)/4 = 0.0458, and for kFlat B = kEndUbMax
+// (the flat map is linear: the argument is scale-free).
+constexpr float kEndStepMax = 0.0625f;
+constexpr float kEndLoMin = 0x1p-20f;
+constexpr float kEndLoMax = 0.75f;
+constexpr float kEndUMax = 0x1p20f;
+constexpr float kEndUbMax = 0x1p40f;
+constexpr float kEndProd = 0.05f;
 
 // tol: GEO_MODE_ADAPTIVE local error tolerance in u (<= 0: the default 1e-6).
 GEO_HD PixelConsts make_consts(float rs, float sphere_r, float r, float step, uint32_t max_steps,
@@ -204,6 +224,19 @@ GEO_HD PixelConsts make_consts(float rs, float sphere_r, float r, float step, ui
         k.stop_lo = above0 ? k.SUp : k.BD;
         k.stop_hi = above0 ? k.HU : k.SU;
         k.stop_bits = (above0 ? 1u : 0u) | ((max_steps != 0u && k.u0 > 0.0f) ? 4u : 0u);
+        // the kTestEnd selector (every compare is false for a NaN operand)
+        bool end_ok = above0 && k.kind != kCurvedIn && step >= kHorizonStepMin && step <= kEndStepMax &&
+                      k.stop_lo >= kEndLoMin && k.U0 <= kEndUMax;
+        float B = kEndUbMax;
+        if (k.kind == kCurvedOut) {
+            // w = 1/(20 h) - 2 h bounds sqrt(B^2 + 1); B rounded down by 2^-20
+            const float w = kEndProd / step - 2.0f * step;
+            end_ok = end_ok && k.stop_lo <= kEndLoMax && w >= 1.0f;
+            B = end_ok ? __builtin_sqrtf((w - 1.0f) * (w + 1.0f)) * (1.0f - 0x1p-20f) : 0.0f;
+        }
+        k.end_lo = end_ok ? -B : 0.0f;
+        k.end_hi = end_ok ? kEndUbMax : 0.0f;
+        k.stop_bits |= end_ok ? 8u : 0u;
     }
     k.tolU = k.scale * (tol > 0.0f ? tol : kAdaptiveDefaultTol);
     k.tolG = k.tolU * (1.0f / 64.0f);
@@ -377,6 +410,12 @@ GEO_HD bool in_ballot_(uint64_t m) { return m != 0; }
 #define GEO_RARE() ((void)0)
 #endif
 
+// Diagnostic builds count the waves by the loop they take (geo_render.hip,
+// GEO_WAVE_LOG); nothing otherwise.
+#if !defined(GEO_LOOP_COUNT)
+#define GEO_LOOP_COUNT(end_test) ((void)0)
+#endif
+
 // Stop flag of one accepted step (reference order: crossing :150, escape
 // :184, loop test :134-135).  The integration ends at the first crossing, so
 // "above the sphere" (U > SU) is fixed for the whole integration and frame-
@@ -488,11 +527,59 @@ GEO_HD float max3_(float a, float b, float c) {
 //             below lo or the maximum above hi (the ray can graze the sphere,
 //             entering and leaving within a group), or state G outside.
 //   kTestEach (kCurvedIn): the reference's compound test on every state.
-// Round 2 tested state G alone, which is exact only while no state leaves the
-// interval and comes back within a group; a near-radial outgoing ray at a
-// large step breaks that (RK4 overshoots U = 0, where F(U) = U^2 - U > 0
-// turns it back: seed 70751).  For G = 4 the minimum is one v_min3_f32: 4
-// VALU per group against 2 for state G alone.
+//   kTestEnd  (kTestLow frames, for the waves whose lanes all pass the
+//             selector of make_consts; chosen per wave in geodesic_angle_v):
+//             state G alone, below lo in an A group of the pair loop and
+//             outside [lo, hi] (or NaN) in a B group: 3 VALU per pair of
+//             groups against kTestLow's 7.  See "The end-state test" below.
+// Round 2 tested state G alone on every frame, which is exact only while no
+// state leaves the interval and comes back within a group; a near-radial
+// outgoing ray at a large step breaks that (RK4 overshoots U = 0, where
+// F(U) = U^2 - U > 0 turns it back: seed 70751).  For G = 4 the minimum is one
+// v_min3_f32: 4 VALU per group against 2 for state G alone.
+//
+// The end-state test.  kTestEnd equals kTestLow iff, within a group, a first
+// state below lo is followed only by states below lo (finite ones): (P).  A
+// group has at most 3 steps after such a state.  Write W = -U' and eps = 2^-24;
+// every f32 operation rounds monotonically and keeps the sign of its exact
+// result, which makes the sign arguments below exact.  F(x) >= -1/4 for every
+// x, F <= 0 on [0, 1], |F(x)| <= x there, and F(x) <= m + m^2 on [-m, 0]
+// (kFlat: F = -x, so F <= 0 on x >= 0 and F <= m on [-m, 0]: no m^2 and no
+// upper limit; the kCurvedOut constants below cover it).
+//  (1) Bound on W.  A step raises W by at most h/4 (1 + eps), and only by
+//      stages in (0, 1), where U falls by at least h W (1 - 3 h^2).  Summed
+//      over a run of states with U' <= 0 in [lo, 3/2] (the discrete form of
+//      the first integral U'^2 + U^2 - 2/3 U^3 of U'' = U^2 - U, with the
+//      potential's 1/3 replaced by 2 * 1/4 * 1.02):
+//          W^2 <= W_0^2 + 0.53 + (h/4) W,
+//      plus h^2 W per step begun above U = 1 (at most 0.6 h in all) and 3h/4
+//      for the group's last three steps.  W_0 is |UB0| <= B for an outgoing
+//      lane and at most h/4 (1 + eps) after a step that began with U' > 0 (a
+//      falling lane that turns back), so every state the argument looks at
+//      has  W <= sqrt(B^2 + 0.53) + 1.7 h < Wb = sqrt(B^2 + 1) + 2 h.
+//      A state with U' > h/8 (1 + 2 eps) steps to NU >= U + h U' - h^2/8 >= lo:
+//      a falling lane of any UB0 cannot cross lo before it turns, so the
+//      lane bound is one-sided (UB0 <= kEndUbMax keeps inf and NaN out).
+//  (2) The crossing step, from (U, -W) or (U, +b) with U >= lo to NU < lo:
+//      h W <= 1/20 and lo <= 3/4 give U <= lo + h W + h^2/8 < 0.81, so the
+//      stages lie in [-h W, 0.81] and NW >= W (1 - 2 h^2) >= 0; for b > 0,
+//      NU < U needs b < h/2 |F|(1 + 3 h^2) while NU' = b - h |F| (1 - 3 h^2)
+//      with |F| >= |F(lo)| / 2 > 0 (lo >= 2^-20: every term is a normal
+//      number).  So the first state below lo has U' <= 0.
+//  (3) The steps after it.  A = the largest W so far in the group.  Below
+//      zero U falls by at most h W (1 + eps) per step, so the stages of these
+//      steps are above -m, m <= 5 h A (1 + eps) <= 1 (that is h A <= 1/5),
+//      every F <= 2 m, and per step  W' >= W - 10 h^2 A,  whence
+//      W >= A (1 - 40 h^2) > 0 through the group (h <= 1/16), and
+//      NU <= U - h W + h^2/2 * 2 m <= U - h A (1 - 40 h^2 - 5 h^2) <= U < lo.
+//      With no stage below zero the step is monotone outright (all F <= 0:
+//      NU <= U, NW >= W).  Every value is finite.
+// The selector requires h Wb <= 1/20, four times inside (3)'s 1/5; the B, lo
+// and h of tests/native/exit_test_host.cpp sit on both sides of each limit.
+// (1) is the loosest step (its sums are bounded with round constants, not
+// term by term); what it has to deliver is W within 4 Wb.  With the end-state
+// test forced on lanes outside the bound, the first differences from the exact
+// test appear at h |UB0| = 135 (h = 1/16) and 537 (h = pi/100).
 // hipcc takes the ballot of a single compare as its mask but rebuilds any
 // other condition through a VGPR (two VALU), so the compares are balloted one
 // by one and ORed in scalar ops; the compound test is ORed first and balloted
@@ -500,10 +587,14 @@ GEO_HD float max3_(float a, float b, float c) {
 constexpr int kTestLow = 0;
 constexpr int kTestBoth = 1;
 constexpr int kTestEach = 2;
+constexpr int kTestEnd = 3;
 
 template <int G, int KIND, int TEST>
 GEO_HD uint64_t group_stop_(const StopTest<KIND>& stop_at, const float (&ou)[G], const float (&ob)[G]) {
-    if constexpr (TEST == kTestEach || G == 1) {
+    if constexpr (TEST == kTestEnd) {
+        const float last = ou[G - 1];
+        return ballot_(med3_(last, stop_at.lo, stop_at.hi) != last);
+    } else if constexpr (TEST == kTestEach || G == 1) {
         bool s = false;
 #pragma unroll
         for (int j = 0; j < G; ++j) s = s | stop_at(ou[j], ob[j]);
@@ -590,7 +681,9 @@ GEO_HD uint32_t run_groups_pp(const StopTest<KIND>& stop_at, uint32_t ngroups, u
     uint32_t rem = ngroups >> 1;
     while (rem != 0) {
         if (in_ballot_(live)) group_steps_<G, KIND>(xu, xb, h, hh, hh2, hhh, h6, h2_6, au, ab);
-        uint64_t hit = (TEST == kTestLow ? group_low_<G>(stop_at.lo, au) : group_stop_<G, KIND, TEST>(stop_at, au, ab)) &
+        uint64_t hit = (TEST == kTestLow   ? group_low_<G>(stop_at.lo, au)
+                        : TEST == kTestEnd ? ballot_(au[G - 1] < stop_at.lo)
+                                           : group_stop_<G, KIND, TEST>(stop_at, au, ab)) &
                        live;
         --rem;
         if (hit != 0) {
@@ -626,7 +719,7 @@ GEO_HD uint32_t run_groups_pp(const StopTest<KIND>& stop_at, uint32_t ngroups, u
         // branch: a pair without stops ends in the counter's compare alone
         if (hit != 0) {
             uint64_t in_a = 0;
-            if constexpr (TEST == kTestLow) {
+            if constexpr (TEST == kTestLow || TEST == kTestEnd) {
                 // A stops above hi (or at a NaN), left to this test: a_G is
                 // then above hi or NaN.  The A group's start state X is B's
                 // end now; the replay (geodesic_finish) reads it only as the
@@ -731,14 +824,11 @@ GEO_HD float geodesic_finish(const PixelConsts& k, const StopTest<KIND>& stop_at
 // saved tests; DESIGN.md §4, tools/ubench/loop_ab.hip at 3cd1aa2)
 constexpr int kGroup = 4;
 
-// Traveled angle of the ray at angle theta to the black hole, or kNoValue.
-// *steps = executed main-loop RK4 steps.  KIND: the integration kind
-// (geodesic_kind); LOOP = RK4 steps per exit test.
-template <int KIND, int LOOP = kGroup>
-GEO_HD float geodesic_angle_v(const PixelConsts& k, float st, float ct, float rct, uint32_t* steps) {
-    *steps = 0;
-    float U, UB, early;
-    if (!geodesic_init<KIND>(k, st, ct, rct, &early, &U, &UB)) return early;
+// geodesic_angle_v after its set-up, from the scaled initial state (U, UB).
+// FORCE: kTestLow or kTestEnd runs that loop on every kTestLow frame,
+// whatever the selector says (tests/native/exit_test_host.cpp).
+template <int KIND, int LOOP = kGroup, int FORCE = -1>
+GEO_HD float geodesic_run_(const PixelConsts& k, float U, float UB, uint32_t* steps) {
     float h = k.step, hh = k.hh, hh2 = k.hh2, hhh = k.hhh, h6 = k.h6, h2_6 = k.h2_6;
     // Main loop (:134-191), restructured for the wave64 VALU: per step the
     // lane-exit flag is StopTest (crossing | escape | horizon); the budget
@@ -773,13 +863,35 @@ GEO_HD float geodesic_angle_v(const PixelConsts& k, float st, float ct, float rc
     if constexpr (KIND == kCurvedIn)
         it = run_groups_pp<G, KIND, kTestEach>(stop_at, ngroups, ngroups * (uint32_t)G, h, hh, hh2, hhh, h6, h2_6,
                                                su_, sb_);
-    else if (stop_at.above0)  // frame-uniform
-        it = run_groups_pp<G, KIND, kTestLow>(stop_at, ngroups, ngroups * (uint32_t)G, h, hh, hh2, hhh, h6, h2_6,
-                                              su_, sb_);
-    else
+    else if (stop_at.above0) {  // frame-uniform
+        // kTestEnd where the frame admits it and every lane of the wave that
+        // enters the loop is inside the lane bound (one v_med3_f32 and a
+        // compare per pixel; the branch is wave-uniform)
+        bool end_test = FORCE == kTestEnd;
+        if constexpr (FORCE < 0)
+            end_test = (k.stop_bits & 8u) != 0 && (ballot_(true) & ~ballot_(med3_(UB, k.end_lo, k.end_hi) == UB)) == 0;
+        GEO_LOOP_COUNT(end_test);
+        if (end_test)
+            it = run_groups_pp<G, KIND, kTestEnd>(stop_at, ngroups, ngroups * (uint32_t)G, h, hh, hh2, hhh, h6, h2_6,
+                                                  su_, sb_);
+        else
+            it = run_groups_pp<G, KIND, kTestLow>(stop_at, ngroups, ngroups * (uint32_t)G, h, hh, hh2, hhh, h6,
+                                                  h2_6, su_, sb_);
+    } else
         it = run_groups_pp<G, KIND, kTestBoth>(stop_at, ngroups, ngroups * (uint32_t)G, h, hh, hh2, hhh, h6, h2_6,
                                                su_, sb_);
     return geodesic_finish<G, KIND>(k, stop_at, it, su_, sb_, steps);
+}
+
+// Traveled angle of the ray at angle theta to the black hole, or kNoValue.
+// *steps = executed main-loop RK4 steps.  KIND: the integration kind
+// (geodesic_kind); LOOP = RK4 steps per exit test.
+template <int KIND, int LOOP = kGroup>
+GEO_HD float geodesic_angle_v(const PixelConsts& k, float st, float ct, float rct, uint32_t* steps) {
+    *steps = 0;
+    float U, UB, early;
+    if (!geodesic_init<KIND>(k, st, ct, rct, &early, &U, &UB)) return early;
+    return geodesic_run_<KIND, LOOP>(k, U, UB, steps);
 }
 
 // Runtime-dispatched form (host tests); the kernel instantiates per kind.

@@ -26,6 +26,18 @@
 #include <vector>
 
 #include "../../include/geo/geo.h"
+#if defined(GEO_WAVE_LOG)
+// Diagnostic build only: waves of the direct-mode loop by the exit test they
+// take ([0] kTestLow, [1] kTestEnd; geo_pixel.h), counted by each wave's first
+// live lane (geo_debug_loop_waves reads and clears them).
+static __device__ unsigned long long g_loop_waves[2];
+#define GEO_LOOP_COUNT(end_test)                                                              \
+    do {                                                                                      \
+        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) ==             \
+            (unsigned)__builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))                     \
+            atomicAdd(&g_loop_waves[(end_test) ? 1 : 0], 1ull);                               \
+    } while (0)
+#endif
 #include "geo_ctx.h"
 #include "geo_band.h"
 #include "geo_disk.h"
@@ -2147,6 +2159,18 @@ int geo_set_dispatch(geo_ctx* c, int mode, uint32_t period) {
 int geo_debug_set_wave_log(geo_ctx* c, void* log) {
     if (!c) return GEO_EINVAL;
     c->wave_log = (unsigned long long*)log;
+    return GEO_OK;
+}
+
+// Diagnostic build only: out[0], out[1] = the waves that took the kTestLow and
+// the kTestEnd loop since the last call (after a device synchronisation).
+extern "C" int geo_debug_loop_waves(geo_ctx* c, unsigned long long* out) {
+    if (!c || !out) return GEO_EINVAL;
+    const unsigned long long zero[2] = {0, 0};
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_waves), sizeof zero) != hipSuccess ||
+        hipMemcpyToSymbol(HIP_SYMBOL(g_loop_waves), zero, sizeof zero) != hipSuccess)
+        return GEO_EINVAL;
     return GEO_OK;
 }
 #endif
