@@ -53,8 +53,11 @@ extern "C" {
                                    launches (geo_render_band_set_frames / _batch);
                                    (still 8, additions only, announced by GEO_HAS_DISK:
                                    GEO_FLAG_DISK, geo_set_disk, geo_clear_disk,
-                                   geo_disk_hits_next_render) */
+                                   geo_disk_hits_next_render;
+                                   announced by GEO_HAS_DISK_SHIFT: geo_disk_shift,
+                                   geo_set_disk_shift, geo_disk_shift_next_render) */
 #define GEO_HAS_DISK 1
+#define GEO_HAS_DISK_SHIFT 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -134,9 +137,12 @@ typedef enum geo_status {
                                    and radial cases: an observer inside the photon sphere)
                                    draws no disk.  Follow-ups, not in this ABI: GEO_FLAG_RING_F64
                                    on disk frames, the batched entry points and multi-GPU
-                                   launches, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE,
-                                   Doppler and redshift shading. */
+                                   launches, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE.
+                                   With geo_set_disk_shift the hits are shaded by their
+                                   Doppler and redshift factor. */
 #define GEO_DISK_MAX_CROSSINGS 3
+#define GEO_DISK_G_MAX 16.0f    /* the largest frequency ratio a shaded hit reports
+                                   (geo_set_disk_shift; csrc/geo_disk.h) */
 
 /* Observer motion states, ObserverState (SR/simulation/observer.rs:12-16). */
 #define GEO_OBSERVER_UNMOVING 0
@@ -235,6 +241,41 @@ int geo_clear_disk(geo_ctx* ctx);
  * Consumed by the next render call whether it succeeds or not (the idiom of
  * geo_time_next_render); a render without GEO_FLAG_DISK writes nothing. */
 int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
+
+/* Doppler and redshift shading of the disk (csrc/geo_disk.h).  The disk's
+ * matter moves on circular geodesics about spin * normal (spin = +1: the
+ * sense in which the disk's azimuth U grows; -1: the other), and a hit at
+ * radius r is seen at the frequency ratio (received / emitted, c = 1)
+ *   g = sqrt(1 - 1.5 rs/r) / sqrt(1 - rs/r_obs)
+ *       / (1 + spin sqrt(rs / (2 r^3)) b w) * g_obs,  clamped to 0..GEO_DISK_G_MAX,
+ * b the ray's impact parameter, b w its angular momentum about the disk axis
+ * and g_obs the moving observer's own Doppler factor.  The hit's texture
+ * sample has R, G and B multiplied by min(gain * g^exponent, 65536), rounded
+ * and saturated at 255, before it is blended; alpha is kept (exponent 4:
+ * bolometric intensity; 3: specific intensity; 0 with gain 1: the unshaded
+ * bytes). */
+typedef struct geo_disk_shift {
+    int32_t spin;      /* +1 or -1 */
+    uint32_t exponent; /* 0..4 */
+    float gain;        /* finite, > 0 */
+} geo_disk_shift;
+
+/* Turns the shading on for this context's GEO_FLAG_DISK renders, or off with
+ * NULL (they are then byte for byte the unshaded ones).  GEO_EINVAL for a spin
+ * other than +1 or -1, exponent > 4 or a gain that is not finite and
+ * positive; a refused call leaves the state as it was.  The state is kept
+ * across geo_set_disk (a texture can be swapped under it) and cleared by
+ * geo_clear_disk.  While it is set a GEO_FLAG_DISK render needs circular
+ * orbits down to the inner edge: rs == 0 or r_in > 1.5 rs (GEO_EINVAL
+ * otherwise, at render time).  The combinations GEO_FLAG_DISK refuses stay
+ * refused. */
+int geo_set_disk_shift(geo_ctx* ctx, const geo_disk_shift* shift);
+/* The next render of this context writes its hits' frequency ratios to out_g
+ * (device, nrows*width*3 floats, laid out as the render's rows): element k of
+ * a pixel is the g of crossing k, or 0 when that crossing is not a hit.
+ * Armed and consumed as geo_disk_hits_next_render's buffer is; written only
+ * by a shaded GEO_FLAG_DISK render. */
+int geo_disk_shift_next_render(geo_ctx* ctx, float* out_g);
 
 /* Uploads a ray fan of n >= 2 nodes (host memory, copied synchronously after
  * the last solve and draws of the buffer it goes to; geo_solve_ray_fan

@@ -57,6 +57,18 @@ int geo_render_cpu_disk(const geo_frame* frame, const geo_scene* scene, const ui
                         const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h,
                         float* out_hits);
 
+/* geo_render_cpu_disk with the shading of geo_set_disk_shift (geo.h): shift
+ * NULL draws the unshaded disk; otherwise its fields and the r_in > 1.5 rs
+ * rule are checked as the device checks them.  out_g (optional, host):
+ * nrows*width*3 floats, the layout of geo_disk_shift_next_render, written
+ * only when shift is given.  Output equal to the GPU's bit for bit. */
+int geo_render_cpu_disk_shift(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8, uint32_t sky_w,
+                              uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width, uint32_t height,
+                              uint32_t row0, uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8,
+                              uint8_t* out_mask, float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                              const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h,
+                              float* out_hits, const geo_disk_shift* shift, float* out_g);
+
 #ifdef __cplusplus
 }
 #endif

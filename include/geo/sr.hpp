@@ -286,6 +286,19 @@ struct ThinDisk {
     Image texture;
     float r_in = 0.0f, r_out = 0.0f;
     Vec3 normal{0.0f, 0.0f, 1.0f}, axis{1.0f, 0.0f, 0.0f};
+    // Doppler and redshift shading (geo_set_disk_shift): off unless set_shift
+    // is called; spin +1 orbits in the sense of growing azimuth.
+    bool shifted = false;
+    geo_disk_shift shift{1, 4u, 1.0f};
+    ThinDisk& set_shift(int32_t spin = 1, uint32_t exponent = 4u, float gain = 1.0f) {
+        shift = geo_disk_shift{spin, exponent, gain};
+        shifted = true;
+        return *this;
+    }
+    ThinDisk& clear_shift() {
+        shifted = false;
+        return *this;
+    }
 };
 
 // ---- BasicSphereBuffer (basic_sphere_buffer.rs) -------------------------
@@ -334,6 +347,7 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
     void set_thin_disk(const ThinDisk& d) {
         const geo_disk gd{d.r_in, d.r_out, {d.normal.x, d.normal.y, d.normal.z}, {d.axis.x, d.axis.y, d.axis.z}};
         check(geo_set_disk(ctx_->get(), &gd, d.texture.rgba.data(), d.texture.width, d.texture.height), "geo_set_disk");
+        check(geo_set_disk_shift(ctx_->get(), d.shifted ? &d.shift : nullptr), "geo_set_disk_shift");
         disk_ = true;
     }
 

@@ -80,6 +80,16 @@ class GeoDisk(ctypes.Structure):
     ]
 
 
+class GeoDiskShift(ctypes.Structure):
+    """geo_disk_shift: Doppler and redshift shading of the disk (geo_set_disk_shift)."""
+
+    _fields_ = [
+        ("spin", ctypes.c_int32),
+        ("exponent", ctypes.c_uint32),
+        ("gain", ctypes.c_float),
+    ]
+
+
 assert ctypes.sizeof(GeoFrame) == 208
 assert ctypes.sizeof(GeoScene) == 32
 
@@ -98,6 +108,8 @@ SIGNATURES = {
     "geo_set_disk": (_int, [_vp, ctypes.POINTER(GeoDisk), _vp, _u32, _u32]),
     "geo_clear_disk": (_int, [_vp]),
     "geo_disk_hits_next_render": (_int, [_vp, _vp]),
+    "geo_set_disk_shift": (_int, [_vp, ctypes.POINTER(GeoDiskShift)]),
+    "geo_disk_shift_next_render": (_int, [_vp, _vp]),
     "geo_set_fan": (_int, [_vp, _vp, _u32]),
     "geo_solve_ray_fan": (_int, [_vp, _f64, _f64, _u32, _f64, _u32, _f64, _vp, _vp]),
     "geo_render_rows": (

@@ -158,6 +158,27 @@ class Context:
             raise ValueError("buf must be float32")
         check("geo_disk_hits_next_render", lib.geo_disk_hits_next_render(self._h, _ptr(buf)))
 
+    def set_disk_shift(self, spin: int = 1, exponent: int = 4, gain: float = 1.0) -> None:
+        """geo_set_disk_shift: shade the disk's hits by their Doppler and redshift factor g
+        (matter on circular orbits about spin * normal): R, G, B times min(gain * g**exponent,
+        65536).  Kept across set_disk, cleared by clear_disk or clear_disk_shift."""
+        sh = _lib.GeoDiskShift(spin, exponent, gain)
+        check("geo_set_disk_shift", lib.geo_set_disk_shift(self._h, ctypes.byref(sh)))
+
+    def clear_disk_shift(self) -> None:
+        check("geo_set_disk_shift", lib.geo_set_disk_shift(self._h, None))
+
+    def disk_shift_next_render(self, buf) -> None:
+        """geo_disk_shift_next_render: the next render, if it is a shaded disk render, writes
+        the 3 g slots of every pixel of its rows into `buf` (a contiguous float32 device
+        tensor; the caller sizes it nrows*width*3)."""
+        _check_buffer("buf", buf, 0, None)
+        import torch
+
+        if buf.dtype != torch.float32:
+            raise ValueError("buf must be float32")
+        check("geo_disk_shift_next_render", lib.geo_disk_shift_next_render(self._h, _ptr(buf)))
+
     def set_fan(self, fan: np.ndarray) -> None:
         a = np.ascontiguousarray(fan, dtype=np.float32)
         check("geo_set_fan", lib.geo_set_fan(self._h, a.ctypes.data, a.size))

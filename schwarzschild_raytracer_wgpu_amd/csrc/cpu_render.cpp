@@ -47,6 +47,10 @@ struct CpuJob {
     const uint32_t* dtex;
     uint32_t dw, dh;
     float* hits;
+    // geo_render_cpu_disk_shift: the shading's constants and the optional g slots
+    bool shift;
+    geo::DiskShift sk;
+    float* gs;
 };
 
 float geodesic(const CpuJob& j, float st, float ct, float rct, uint32_t* n) {
@@ -165,8 +169,12 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
     for (uint32_t ly = tid; ly < j.nrows; ly += nthreads) {
         const uint32_t py = j.row0 + ly * j.row_step;
         for (uint32_t px = 0; px < j.width; ++px) {
-            float c2x, c2y, c2z;
-            geo::pixel_central_dir(j.cam, j.f->movement_to_central, psi_k, j.kt, px, py, &c2x, &c2y, &c2z);
+            float c2x, c2y, c2z, g_obs = 1.0f;
+            if (j.shift)
+                geo::pixel_central_dir_g(j.cam, j.f->movement_to_central, psi_k, j.kt, px, py, &c2x, &c2y, &c2z,
+                                         &g_obs);
+            else
+                geo::pixel_central_dir(j.cam, j.f->movement_to_central, psi_k, j.kt, px, py, &c2x, &c2y, &c2z);
             const float st = geo::central_sin(c2z);
             const float ct = geo::central_rho(c2x, c2y);
             const float rct = geo::rcpf_(ct);
@@ -186,8 +194,15 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             if (!bh || j.uv) geo::sky_uv(j.f->central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
             const size_t o = (size_t)ly * j.width + px;
             const uint32_t base = bh ? geo::kBlackRGBA : geo::sample_sky(fetch, j.sw, j.sh, j.opaque, U, V);
-            j.rgba[o] = geo::disk_shade(j.dk, k, dr, Uk, n, ang, base, dsample,
-                                        j.hits ? j.hits + o * (2u * geo::kDiskMaxCrossings) : nullptr);
+            float* const hits = j.hits ? j.hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
+            if (j.shift) {
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(j.dk, j.sk, dr, ct, g_obs, &sr);
+                j.rgba[o] = geo::disk_shade_shift(j.dk, k, dr, j.sk, sr, Uk, n, ang, base, dsample, hits,
+                                                  j.gs ? j.gs + o * geo::kDiskMaxCrossings : nullptr);
+            } else {
+                j.rgba[o] = geo::disk_shade(j.dk, k, dr, Uk, n, ang, base, dsample, hits);
+            }
             if (j.mask) j.mask[o] = bh ? 1 : 0;
             if (j.uv) {
                 j.uv[2 * o] = U;
@@ -260,7 +275,8 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
                     uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width, uint32_t height, uint32_t row0,
                     uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
                     float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, const geo_disk* disk,
-                    const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits) {
+                    const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits,
+                    const geo_disk_shift* shift, float* out_g) {
     if (!frame || !scene || !sky_rgba8 || !out_rgba8 || sky_w == 0 || sky_h == 0 || width == 0 || height == 0 ||
         row_step == 0 || width > (1u << 20) || height > (1u << 20))
         return GEO_EINVAL;
@@ -288,6 +304,10 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
         if (!(disk->r_in > 0.0f) || !(disk->r_in < disk->r_out) || !(disk->r_out < 3.0e38f)) return GEO_EINVAL;
         if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < disk->r_in)) ||
             !(disk->r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
+            return GEO_EINVAL;
+        // geo_set_disk_shift's rules and the render's r_in > 1.5 rs
+        if (shift && ((shift->spin != 1 && shift->spin != -1) || shift->exponent > 4u || !(shift->gain > 0.0f) ||
+                      !(shift->gain <= 3.4028234e38f) || (scene->rs > 0.0f && !(disk->r_in > 1.5f * scene->rs))))
             return GEO_EINVAL;
     }
     if (scene->mode == GEO_MODE_FAN && (!fan || n_fan < 2)) return GEO_EINVAL;
@@ -336,6 +356,9 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.dw = disk_w;
     j.dh = disk_h;
     j.hits = out_hits;
+    j.shift = disk && shift;
+    j.gs = out_g;
+    if (j.shift) j.sk = geo::disk_shift_consts(frame->central_to_uv, scene->rs, scene->r_obs, shift->spin, shift->exponent, shift->gain);
     std::vector<uint32_t> dtex;
     if (disk) {
         if (!geo::disk_consts(frame->central_to_uv, disk->normal, disk->axis, disk->r_in, disk->r_out, j.k, &j.dk))
@@ -384,7 +407,7 @@ extern "C" int geo_render_cpu(const geo_frame* frame, const geo_scene* scene, co
                               unsigned long long* steps_total) {
     return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, nullptr, nullptr, 0, 0,
-                           nullptr);
+                           nullptr, nullptr, nullptr);
 }
 
 extern "C" int geo_render_cpu_disk(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
@@ -396,5 +419,18 @@ extern "C" int geo_render_cpu_disk(const geo_frame* frame, const geo_scene* scen
     if (!disk) return GEO_EINVAL;
     return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
-                           disk_h, out_hits);
+                           disk_h, out_hits, nullptr, nullptr);
+}
+
+extern "C" int geo_render_cpu_disk_shift(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                         uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                         uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                         uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                         float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                         const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                         uint32_t disk_h, float* out_hits, const geo_disk_shift* shift, float* out_g) {
+    if (!disk) return GEO_EINVAL;
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, shift, shift ? out_g : nullptr);
 }

@@ -110,6 +110,12 @@ struct geo_ctx {
     uint32_t* disk_tex;
     uint32_t disk_w, disk_h, disk_bytes;
     float* hits_next;
+    // geo_set_disk_shift: the disk's Doppler and redshift shading (kept across
+    // geo_set_disk, cleared by geo_clear_disk) and the g buffer of
+    // geo_disk_shift_next_render (the next render's alone)
+    bool shift_set;
+    geo_disk_shift shift;
+    float* g_next;
 #if defined(GEO_WAVE_LOG)
     unsigned long long* wave_log;  // diagnostic build only (geo_debug_set_wave_log)
 #endif

@@ -322,4 +322,137 @@ GEO_HD uint32_t disk_shade(const DiskConsts& d, const PixelConsts& k, const Disk
     return c;
 }
 
+// ---- Doppler and redshift shading (geo_set_disk_shift) ------------------
+// The disk's matter at radius r moves on circular geodesics about spin * n
+// (spin = +1: the sense in which the disk's azimuth U grows) with angular
+// velocity Omega = sqrt(rs / (2 r^3)) (c = 1, scene units; circular timelike
+// orbits need r > 1.5 rs: a shifted render is refused unless r_in > 1.5 rs,
+// or rs = 0, where Omega = 0).  A hit's received / emitted frequency ratio is
+//   g = g_grav g_dopp g_obs,
+//   g_grav = sqrt(1 - 1.5 rs/r) / sqrt(1 - rs/r_obs)   (the emitter's time
+//            dilation on its orbit; the static observer's potential),
+//   g_dopp = 1 / (1 + spin Omega b w),  b = r_obs cos(theta) / sqrt(1 - rs/r_obs)
+//            (the ray's impact parameter, GEO_FLAG_RING_F64's b) and
+//            w = sigma (z x q) . N = sigma (N_y cos phi - N_x sin phi): the
+//            photon travels the traced ray backwards, so its angular momentum
+//            about the disk axis is -b w per unit energy, conserved along the
+//            ray (one w for all three crossings).  sigma = sign(det M2): the
+//            disk's sense of rotation is defined in the sky texture's frame
+//            (e_y = n x e_x there), a cross product of central-frame
+//            components has the other handedness when central_to_uv is a
+//            reflection, and the observer's pipeline produces one (det = -1),
+//   g_obs  = the observer's own Doppler factor (pixel_central_dir_g).
+// The signs were checked against an f64 restatement that uses the ray's local
+// tangent at the hit instead of the conserved angular momentum
+// (tests/disk_shift_ref.py) and by the approaching / receding side test.
+// The f32 specification (the operations of geo_math.h / geo_pixel.h):
+//   per frame (host, f64, each rounded once): sb = sigma spin r_obs / sqrt(1 - rs/r_obs),
+//     ih = 1 / sqrt(1 - rs/r_obs)
+//   per ray:  w' = fma(N_y, cos phi, -(N_x sin phi));  bw = (rho sb) w'
+//     (rho = central_rho = cos theta);  gk = g_obs ih
+//   per hit (r of disk_hit):  ir = rcpf_(r);  x = rs ir;
+//     den = fma(bw ir, sqrtf_(0.5 x), 1);
+//     g = med3((sqrtf_(fma(-1.5, x, 1)) rcpf_(den)) gk, 0, GEO_DISK_G_MAX)
+//     (a NaN, from a radicand an ulp below 0, becomes 0)
+//   colour: gp = g^p by p multiplications from 1 (p = exponent, 0..4);
+//     m = min(gain gp, 65536);  each of R, G, B of the hit's texture sample:
+//     min(255, floor_i32_(fma(c, m, 0.5))); alpha kept.  m = 1 keeps the bytes.
+// GEO_DISK_G_MAX = 16: g^4 <= 65536 = the cap of m, so no power overflows and
+// fma(c, m, 0.5) < 2^24 + 1 stays far inside floor_i32_'s range.  Physical
+// ratios reach it only for an observer within 0.4 % of the horizon or a ray
+// within an ulp of Omega b = 1.
+constexpr float kDiskGMax = 16.0f;     // GEO_DISK_G_MAX
+constexpr float kDiskMMax = 65536.0f;  // the cap of the colour multiplier
+
+struct DiskShift {
+    float sb;  // sign(det M2) * spin * r_obs / sqrt(1 - rs/r_obs)
+    float ih;  // 1 / sqrt(1 - rs/r_obs)
+    float gain;
+    uint32_t exponent;
+};
+
+// m2: central_to_uv; rs = 0, or r_obs > rs (GEO_FLAG_DISK's rule); spin = +1 or -1.
+GEO_HD DiskShift disk_shift_consts(const float* m2, float rs, float r_obs, int spin, uint32_t exponent, float gain) {
+    const double h = 1.0 / __builtin_sqrt(1.0 - (double)rs / (double)r_obs);
+    const double a = m2[0], b = m2[1], c = m2[2], d = m2[4], e = m2[5], f = m2[6], g = m2[8], i = m2[9], j = m2[10];
+    const double det = a * (e * j - f * i) - d * (b * j - c * i) + g * (b * f - c * e);
+    DiskShift s;
+    s.sb = (float)((det < 0.0 ? -1.0 : 1.0) * (double)spin * (double)r_obs * h);
+    s.ih = (float)h;
+    s.gain = gain;
+    s.exponent = exponent;
+    return s;
+}
+
+// The ray's shift terms, known before the integration.
+struct DiskShiftRay {
+    float bw;  // spin * b * w (sigma included)
+    float gk;  // g_obs / sqrt(1 - rs/r_obs)
+};
+
+GEO_HD void disk_shift_ray(const DiskConsts& d, const DiskShift& s, const DiskRay& dr, float rho, float g_obs,
+                           DiskShiftRay* r) {
+    const float w = fmaf_(d.N[1], dr.cphi, -(d.N[0] * dr.sphi));
+    r->bw = (rho * s.sb) * w;
+    r->gk = g_obs * s.ih;
+}
+
+// The frequency ratio of a hit at radius r.
+GEO_HD float disk_shift_g(const PixelConsts& k, const DiskShiftRay& sr, float r) {
+    const float ir = rcpf_(r);
+    const float x = k.rs * ir;
+    const float den = fmaf_(sr.bw * ir, sqrtf_(0.5f * x), 1.0f);
+    const float g = (sqrtf_(fmaf_(-1.5f, x, 1.0f)) * rcpf_(den)) * sr.gk;
+    return med3_(g, 0.0f, kDiskGMax);
+}
+
+GEO_HD uint32_t disk_shift_channel_(uint32_t c, float m) {
+    const int32_t v = floor_i32_(fmaf_((float)c, m, 0.5f));
+    return (uint32_t)(v < 255 ? v : 255);
+}
+
+// The texture sample s scaled by the shift g (alpha kept).
+GEO_HD uint32_t disk_shift_colour(const DiskShift& s, float g, uint32_t smp) {
+    float gp = 1.0f;
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) gp = i < s.exponent ? gp * g : gp;
+    const float m = __builtin_fminf(s.gain * gp, kDiskMMax);
+    return disk_shift_channel_(smp & 0xFFu, m) | (disk_shift_channel_((smp >> 8) & 0xFFu, m) << 8) |
+           (disk_shift_channel_((smp >> 16) & 0xFFu, m) << 16) | (smp & 0xFF000000u);
+}
+
+// disk_shade_slot_ with the shift: the scaled sample is what composite_
+// blends; gs (optional): the pixel's 3 g slots (0 where the crossing is no hit).
+template <int S, typename Sample>
+GEO_HD uint32_t disk_shade_shift_slot_(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr,
+                                       const DiskShift& sh, const DiskShiftRay& sr, float Us, uint32_t steps,
+                                       float angle, uint32_t c, const Sample& sample, float* hits, float* gs) {
+    float r = 0.0f, Ud = 0.0f, Vd = 0.0f, g = 0.0f;
+    if (disk_hit(d, k, dr, S, Us, steps, angle, &r, &Ud, &Vd)) {
+        g = disk_shift_g(k, sr, r);
+        c = composite_(disk_shift_colour(sh, g, sample(Ud, Vd)), c);
+    } else {
+        r = 0.0f;
+        Ud = 0.0f;
+    }
+    if (hits) {
+        hits[2 * S] = r;
+        hits[2 * S + 1] = Ud;
+    }
+    if (gs) gs[S] = g;
+    return c;
+}
+
+template <typename Sample>
+GEO_HD uint32_t disk_shade_shift(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr, const DiskShift& sh,
+                                 const DiskShiftRay& sr, const float (&Uk)[kDiskMaxCrossings], uint32_t steps,
+                                 float angle, uint32_t base, const Sample& sample, float* hits, float* gs) {
+    static_assert(kDiskMaxCrossings == 3, "three slots, written out");
+    uint32_t c = base;
+    c = disk_shade_shift_slot_<2>(d, k, dr, sh, sr, Uk[2], steps, angle, c, sample, hits, gs);
+    c = disk_shade_shift_slot_<1>(d, k, dr, sh, sr, Uk[1], steps, angle, c, sample, hits, gs);
+    c = disk_shade_shift_slot_<0>(d, k, dr, sh, sr, Uk[0], steps, angle, c, sample, hits, gs);
+    return c;
+}
+
 }  // namespace geo

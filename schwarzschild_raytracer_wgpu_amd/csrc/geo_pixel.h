@@ -1110,6 +1110,31 @@ GEO_HD void pixel_central_dir(const CameraConsts& cc, const float* m1, float psi
     }
 }
 
+// pixel_central_dir, and in *g_obs the observer's own Doppler factor
+// (received / rest-frame frequency of the light the pixel sees):
+//   g_obs = sqrt(1 - k^2) / (1 - k d_z/|d|) = len * (kt * id),
+// exactly 1 for psi_k = 0 (len * rcpf_(len) need not be).  The direction is
+// pixel_central_dir's, operation for operation.
+GEO_HD void pixel_central_dir_g(const CameraConsts& cc, const float* m1, float psi_k, float kt, uint32_t px,
+                                uint32_t py, float* c2x, float* c2y, float* c2z, float* g_obs) {
+    const float fx = (float)px, fy = (float)py;
+    const float dx = fmaf_(fy, cc.a[0], fmaf_(fx, cc.b[0], cc.c[0]));
+    const float dy = fmaf_(fy, cc.a[1], fmaf_(fx, cc.b[1], cc.c[1]));
+    const float dz = fmaf_(fy, cc.a[2], fmaf_(fx, cc.b[2], cc.c[2]));
+    const float len = sqrtf_(fmaf_(dz, dz, fmaf_(dy, dy, dx * dx)));
+    const float id = rcpf_(fmaf_(-psi_k, dz, len));
+    const float g = kt * id;
+    const float ex = dx * g, ey = dy * g, ez = fmaf_(-psi_k, len, dz) * id;
+    *g_obs = psi_k == 0.0f ? 1.0f : len * g;
+    if (cc.m1_identity) {
+        *c2x = ex;
+        *c2y = ey;
+        *c2z = ez;
+    } else {
+        mat3_mul(m1, ex, ey, ez, c2x, c2y, c2z);
+    }
+}
+
 // floor(x) as an int32 for |x| < 2^31 (the sampler's texel coordinates):
 // one v_cvt_flr_i32_f32 on the device, where hipcc emits v_floor_f32 +
 // v_cvt_i32_f32 (two half-rate opcodes) for the cast of floorf.

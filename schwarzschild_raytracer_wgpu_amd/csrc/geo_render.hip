@@ -43,6 +43,8 @@ static __device__ unsigned long long g_loop_waves[2];
 #include "geo_disk.h"
 #include "geo_pixel.h"
 
+static_assert(geo::kDiskGMax == GEO_DISK_G_MAX, "geo.h announces the header's clamp");
+
 // Work decomposition (measured): 32 x 8-pixel workgroup tiles
 // of 2 x 2 waves of 16 x 4 pixels.  A tile row spans 32 sky texels = one
 // 128-B line, so neighbouring waves share their sky lines in one CU instead of
@@ -813,6 +815,87 @@ __global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a,
     }
 }
 
+// The shifted render (geo_set_disk_shift): the kernel above with the ray's
+// shift terms computed once per lane and the per-hit ones in the hit arm of
+// geo::disk_shade_shift_slot_; the RK4 loop is the plain render's.  A kernel
+// of its own with a further argument, not a parameter of the one above: that
+// one's code, argument segment and resource records stay as they were (a
+// shared inlined body changed its instruction schedule).  The two bodies are
+// kept in step by the CPU path, which has one (run_rows_disk, cpu_render.cpp):
+// both kernels are tested against it bit for bit.
+struct DiskShiftArgs {
+    geo::DiskShift k;
+    float* out_g;  // optional: 3 x g per pixel
+};
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                   const DiskArgs d, const DiskShiftArgs sh) {
+    const FrameK& f = fb.f[0];
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
+    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    uint32_t steps = 0;
+    if (px < a.width && ly < a.nrows && py < a.height) {
+        float c2x, c2y, c2z, g_obs;
+        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                                 &c2x, &c2y, &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        geo::DiskRay dr;
+        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const size_t o = (size_t)ly * a.width + px;
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
+                                                                    kBufferRsrcWord3),
+                                  d.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
+        };
+        geo::DiskShiftRay sr;
+        geo::disk_shift_ray(d.k, sh.k, dr, ct, g_obs, &sr);
+        a.out_rgba[o] = geo::disk_shade_shift(d.k, a.k, dr, sh.k, sr, Uk, steps, ang, base, dsample,
+                                              d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr,
+                                              sh.out_g ? sh.out_g + o * geo::kDiskMaxCrossings : nullptr);
+        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
+        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
+        if (a.out_steps) a.out_steps[o] = steps;
+    }
+    // (every lane of the wave is active again here, as in geo_render_kernel)
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost) {
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1420,6 +1503,7 @@ int geo_clear_disk(geo_ctx* c) {
     }
     c->disk_tex = nullptr;
     c->disk_set = false;
+    c->shift_set = false;
     return GEO_OK;
 }
 
@@ -1468,6 +1552,26 @@ int geo_set_disk(geo_ctx* c, const geo_disk* disk, const uint8_t* rgba8, uint32_
 int geo_disk_hits_next_render(geo_ctx* c, float* out_hits) {
     if (!c || !out_hits) return GEO_EINVAL;
     c->hits_next = out_hits;
+    return GEO_OK;
+}
+
+int geo_set_disk_shift(geo_ctx* c, const geo_disk_shift* shift) {
+    if (!c) return GEO_EINVAL;
+    if (!shift) {
+        c->shift_set = false;
+        return GEO_OK;
+    }
+    if ((shift->spin != 1 && shift->spin != -1) || shift->exponent > 4u || !(shift->gain > 0.0f) ||
+        !(shift->gain <= 3.4028234e38f))
+        return GEO_EINVAL;
+    c->shift = *shift;
+    c->shift_set = true;
+    return GEO_OK;
+}
+
+int geo_disk_shift_next_render(geo_ctx* c, float* out_g) {
+    if (!c || !out_g) return GEO_EINVAL;
+    c->g_next = out_g;
     return GEO_OK;
 }
 
@@ -1669,10 +1773,12 @@ static int launch_frames(const RenderArgs& a, const FrameK* fk, const geo::Pixel
 
 // A GEO_FLAG_DISK frame (geo_render_disk_kernel): launch_tiles' loop on the
 // wave-block grid.
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) <= 4096, "kernel arguments fit 4 KiB");
-template <int KIND>
-static int launch_disk(RenderArgs a, const FrameK& fk, const DiskArgs& d, uint32_t tiles_x, uint32_t tiles_y,
-                       hipStream_t s, hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop) {
+// SHIFT: the shifted render (geo_render_disk_shift_kernel) with its constants *sh (null otherwise).
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskShiftArgs) <= 4096,
+              "kernel arguments fit 4 KiB");
+template <int KIND, bool SHIFT>
+static int launch_disk(RenderArgs a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh, uint32_t tiles_x,
+                       uint32_t tiles_y, hipStream_t s, hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop) {
     FrameBatch<1> fb;
     fb.f[0] = fk;
     a.tiles_x = tiles_x;
@@ -1684,14 +1790,25 @@ static int launch_disk(RenderArgs a, const FrameK& fk, const DiskArgs& d, uint32
         const bool last = y0 + ny >= tiles_y;
         hipEvent_t start = y0 == 0 ? t_start : nullptr;
         hipEvent_t stop = last ? (t_stop ? t_stop : done) : nullptr;
-        hipExtLaunchKernelGGL((geo_render_disk_kernel<KIND>), dim3(wave_block_count(a.launch_tiles)), dim3(64), 0, s,
-                              start, stop, 0, a, fb, d);
+        if constexpr (SHIFT)
+            hipExtLaunchKernelGGL((geo_render_disk_shift_kernel<KIND>), dim3(wave_block_count(a.launch_tiles)),
+                                  dim3(64), 0, s, start, stop, 0, a, fb, d, *sh);
+        else
+            hipExtLaunchKernelGGL((geo_render_disk_kernel<KIND>), dim3(wave_block_count(a.launch_tiles)), dim3(64), 0,
+                                  s, start, stop, 0, a, fb, d);
         if (hipGetLastError() != hipSuccess) return GEO_EHIP;
     }
     if (t_stop && hipEventRecord(done, s) != hipSuccess) return GEO_EHIP;
     return GEO_OK;
 }
 }
+
+// launch_disk<kind, true>.  Defined at the end of this file: the shifted
+// kernels are instantiated there, after every kernel the file had before
+// them, so those keep their places (and their labels) in the code object.
+static int launch_disk_shift(int kind, const RenderArgs& a, const FrameK& fk, const DiskArgs& d,
+                             const DiskShiftArgs& sh, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s,
+                             hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop);
 
 // The order buffers hold at least n tiles (both orders, the costs, the class
 // histograms).  Growing them waits for the context's renders and rebuilds,
@@ -1733,6 +1850,7 @@ static int invalid_call(geo_ctx* c) {
     if (c) {
         c->time_start = c->time_stop = nullptr;
         c->hits_next = nullptr;
+        c->g_next = nullptr;
     }
     return GEO_EINVAL;
 }
@@ -1753,6 +1871,9 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     // geo_disk_hits_next_render's buffer likewise
     float* const out_hits = c->hits_next;
     c->hits_next = nullptr;
+    // and geo_disk_shift_next_render's
+    float* const out_g = c->g_next;
+    c->g_next = nullptr;
     if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
         return GEO_EINVAL;
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
@@ -1790,6 +1911,8 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
         if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < c->disk.r_in)) ||
             !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
             return GEO_EINVAL;
+        // shading: circular timelike orbits down to the inner edge
+        if (c->shift_set && scene->rs > 0.0f && !(c->disk.r_in > 1.5f * scene->rs)) return GEO_EINVAL;
     }
     DeviceGuard g(c->device);
     if (!g.ok) return GEO_EHIP;
@@ -1984,10 +2107,17 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
         d.tex_pitch_b = (c->disk_w + 2u) * 4u;
         d.tex_bytes = c->disk_bytes;
         d.out_hits = out_hits;
-        switch (geo::geodesic_kind(a.k)) {
-            case geo::kCurvedOut: st = launch_disk<geo::kCurvedOut>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop); break;
-            case geo::kCurvedIn: st = launch_disk<geo::kCurvedIn>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop); break;
-            default: st = launch_disk<geo::kFlat>(a, fk[0], d, tiles_x, tiles_y, s, done, t_start, t_stop);
+        if (c->shift_set) {
+            DiskShiftArgs sh;
+            sh.k = geo::disk_shift_consts(frames[0].central_to_uv, scene->rs, scene->r_obs, c->shift.spin, c->shift.exponent, c->shift.gain);
+            sh.out_g = out_g;
+            st = launch_disk_shift(geo::geodesic_kind(a.k), a, fk[0], d, sh, tiles_x, tiles_y, s, done, t_start, t_stop);
+        } else {
+            switch (geo::geodesic_kind(a.k)) {
+                case geo::kCurvedOut: st = launch_disk<geo::kCurvedOut, false>(a, fk[0], d, nullptr, tiles_x, tiles_y, s, done, t_start, t_stop); break;
+                case geo::kCurvedIn: st = launch_disk<geo::kCurvedIn, false>(a, fk[0], d, nullptr, tiles_x, tiles_y, s, done, t_start, t_stop); break;
+                default: st = launch_disk<geo::kFlat, false>(a, fk[0], d, nullptr, tiles_x, tiles_y, s, done, t_start, t_stop);
+            }
         }
     }
     if (st) return st;
@@ -2295,3 +2425,13 @@ int geo_render_band_set_batch(geo_ctx* c, const geo_frame* frames, const geo_sce
 }
 
 }  // extern "C"
+
+static int launch_disk_shift(int kind, const RenderArgs& a, const FrameK& fk, const DiskArgs& d,
+                             const DiskShiftArgs& sh, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s,
+                             hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop) {
+    switch (kind) {
+        case geo::kCurvedOut: return launch_disk<geo::kCurvedOut, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
+        case geo::kCurvedIn: return launch_disk<geo::kCurvedIn, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
+        default: return launch_disk<geo::kFlat, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
+    }
+}

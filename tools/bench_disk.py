@@ -11,6 +11,11 @@ Writes one JSON object (profiles/disk_bench_cfg3.json by default) and prints
 it.
 
   python tools/bench_disk.py [--n 30] [--out profiles/disk_bench_cfg3.json]
+  python tools/bench_disk.py --shift [--n 30] [--out profiles/disk_shift_bench_cfg3.json]
+
+--shift adds the shaded disk frame (geo_set_disk_shift: spin +1, exponent 4,
+gain 1) as a third kind in the same alternation and reports it against the
+unshaded disk frame; its output file is a JSON list that every run appends to.
 """
 from __future__ import annotations
 
@@ -27,8 +32,11 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=30, help="timed renders of each kind (>= 20)")
     p.add_argument("--warmup", type=int, default=40, help="untimed renders of each kind first")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "disk_bench_cfg3.json"))
+    p.add_argument("--shift", action="store_true", help="also time the Doppler-shaded disk frame")
+    p.add_argument("--out")
     args = p.parse_args()
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json")
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
 
@@ -63,13 +71,20 @@ def main():
     # would re-learn at every switch, so each kind runs on its own context
     ctx2 = g.Context(0)
     ctx2.set_sky(make_sky(cfg.sky, cfg.sky_size))
+    kinds = [("plain", ctx2, plain), ("disk", ctx, disk)]
+    if args.shift:
+        ctx3 = g.Context(0)
+        ctx3.set_sky(make_sky(cfg.sky, cfg.sky_size))
+        ctx3.set_disk(make_disk_texture((1024, 128)), r_in, r_out)
+        ctx3.set_disk_shift(1, 4, 1.0)
+        kinds.append(("shift", ctx3, disk))
     for _ in range(args.warmup):
-        ctx2.render_rows(frame, plain, W, H, 0, H, out)
-        ctx.render_rows(frame, disk, W, H, 0, H, out)
+        for _, c, sc in kinds:
+            c.render_rows(frame, sc, W, H, 0, H, out)
     torch.cuda.synchronize()
-    ev = {"plain": [], "disk": []}
+    ev = {k: [] for k, _, _ in kinds}
     for _ in range(args.n):
-        for kind, c, sc in (("plain", ctx2, plain), ("disk", ctx, disk)):
+        for kind, c, sc in kinds:
             a, b = HipEvent(), HipEvent()
             c.time_next_render(a, b)
             c.render_rows(frame, sc, W, H, 0, H, out)
@@ -90,13 +105,28 @@ def main():
         "disk_ms_iqr": float(np.subtract(*np.percentile(ms["disk"], [75, 25]))),
         "disk_over_plain": float(np.median(ms["disk"]) / np.median(ms["plain"])),
         "hit_pixels_per_slot": [int(hv[..., k].sum()) for k in range(3)],
-        "timing": "geo_time_next_render event pairs on each kernel dispatch, plain and disk alternating",
+        "timing": "geo_time_next_render event pairs on each kernel dispatch, the kinds alternating",
     }
+    if args.shift:
+        res.update({
+            "shift": [1, 4, 1.0],
+            "shift_ms_median": float(np.median(ms["shift"])), "shift_ms_min": float(ms["shift"].min()),
+            "shift_ms_iqr": float(np.subtract(*np.percentile(ms["shift"], [75, 25]))),
+            "shift_over_disk": float(np.median(ms["shift"]) / np.median(ms["disk"])),
+            "hit_pixel_share": float(hv.any(axis=-1).float().mean()),
+        })
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    doc = res
+    if args.shift:  # every run is kept
+        doc = []
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                doc = json.load(f)
+        doc.append(res)
     with open(args.out, "w") as f:
-        f.write(json.dumps(res, indent=1) + "\n")
+        f.write(json.dumps(doc, indent=1) + "\n")
 
 
 if __name__ == "__main__":

@@ -7,11 +7,14 @@ the present step of the absent wgpu_renderer loop.
         [--sky eso0932a.jpg --planet world_8k.png --clouds transparent_clouds.png]
         [--frames 60 --orbit 3.2] [--mipmaps] [--fan]
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
+        [--disk-shift SPIN EXP GAIN]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
 images) instead of the reference's scene; --cpu renders it with the CPU path
-(libgeo_cpu.so, the same bytes, no GPU needed).
+(libgeo_cpu.so, the same bytes, no GPU needed).  --disk-shift SPIN EXP GAIN
+shades the disk by its Doppler and redshift factor g (geo_set_disk_shift:
+matter orbiting about SPIN * normal, colours times GAIN * g**EXP).
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -53,20 +56,27 @@ def disk_frame(args):
         sky = np.ascontiguousarray(sky)
         rgba = np.zeros((h, w, 4), np.uint8)
         vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        lib.geo_render_cpu_disk.restype = ctypes.c_int
-        lib.geo_render_cpu_disk.argtypes = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int, vp,
-                                            vp, vp, vp, vp, vp, vp, u32, u32, vp]
-        rc = lib.geo_render_cpu_disk(ctypes.addressof(frame), ctypes.addressof(scene), sky.ctypes.data, sky.shape[1],
-                                     sky.shape[0], None, 0, w, h, 0, h, 1, 0, rgba.ctypes.data, None, None, None, None,
-                                     ctypes.addressof(disk), tex.ctypes.data, tex.shape[1], tex.shape[0], None)
+        shift = None
+        if args.disk_shift:
+            shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
+        lib.geo_render_cpu_disk_shift.restype = ctypes.c_int
+        lib.geo_render_cpu_disk_shift.argtypes = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int,
+                                                  vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
+        rc = lib.geo_render_cpu_disk_shift(ctypes.addressof(frame), ctypes.addressof(scene), sky.ctypes.data,
+                                           sky.shape[1], sky.shape[0], None, 0, w, h, 0, h, 1, 0, rgba.ctypes.data,
+                                           None, None, None, None, ctypes.addressof(disk), tex.ctypes.data,
+                                           tex.shape[1], tex.shape[0], None,
+                                           ctypes.addressof(shift) if shift else None, None)
         if rc != 0:
-            raise SystemExit(f"geo_render_cpu_disk: {rc}")
+            raise SystemExit(f"geo_render_cpu_disk_shift: {rc}")
     else:
         import torch
 
         ctx = g.Context(0)
         ctx.set_sky(sky)
         ctx.set_disk(tex, r_in, r_out, normal=args.disk_normal)
+        if args.disk_shift:
+            ctx.set_disk_shift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
         rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
         ctx.render_rows(frame, scene, w, h, 0, h, rgba)
     if args.out.endswith(".ppm"):
@@ -98,7 +108,9 @@ def main():
     p.add_argument("--disk", type=float, nargs=2, metavar=("R_IN", "R_OUT"),
                    help="the ray-traced thin disk (GEO_FLAG_DISK) over the sky sphere")
     p.add_argument("--disk-normal", type=float, nargs=3, default=(0.0, 0.0, 1.0))
-    p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (geo_render_cpu_disk)")
+    p.add_argument("--disk-shift", type=float, nargs=3, metavar=("SPIN", "EXP", "GAIN"),
+                   help="with --disk: Doppler and redshift shading (geo_set_disk_shift)")
+    p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (geo_render_cpu_disk_shift)")
     p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
     p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
     p.add_argument("--fov", type=float, default=math.pi / 2, help="with --disk")
