@@ -55,9 +55,11 @@ extern "C" {
                                    GEO_FLAG_DISK, geo_set_disk, geo_clear_disk,
                                    geo_disk_hits_next_render;
                                    announced by GEO_HAS_DISK_SHIFT: geo_disk_shift,
-                                   geo_set_disk_shift, geo_disk_shift_next_render) */
+                                   geo_set_disk_shift, geo_disk_shift_next_render;
+                                   announced by GEO_HAS_DISK_BATCH: geo_render_disk_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
+#define GEO_HAS_DISK_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -129,15 +131,19 @@ typedef enum geo_status {
                                    with the reference's 8-bit alpha blend over what the plain
                                    render writes; mask, UV, steps and steps_total are the
                                    plain render's (csrc/geo_disk.h).
-                                   geo_render_rows / _bands / _band_set only, GEO_MODE_DIRECT,
+                                   geo_render_rows / _bands / _band_set for one frame and
+                                   geo_render_disk_batch for up to GEO_MAX_BATCH_FRAMES in
+                                   one launch (the multi-GPU pipeline's batches, a moving
+                                   observer's frames); geo_render_band_set_frames / _batch
+                                   refuse the flag.  GEO_MODE_DIRECT,
                                    with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
                                    and rs < r_in; r_out < sphere_r and r_obs < sphere_r
                                    (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
                                    A ray the reference ends before its loop (its pre-filters
                                    and radial cases: an observer inside the photon sphere)
                                    draws no disk.  Follow-ups, not in this ABI: GEO_FLAG_RING_F64
-                                   on disk frames, the batched entry points and multi-GPU
-                                   launches, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE.
+                                   on disk frames, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS /
+                                   _COMPOSITE.
                                    With geo_set_disk_shift the hits are shaded by their
                                    Doppler and redshift factor. */
 #define GEO_DISK_MAX_CROSSINGS 3
@@ -379,6 +385,28 @@ int geo_render_band_set_batch(geo_ctx* ctx, const geo_frame* frames, const geo_s
                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                               unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for GEO_FLAG_DISK scenes (GEO_HAS_DISK_BATCH): nframes
+ * (1 .. GEO_MAX_BATCH_FRAMES) frames of the context's thin disk in ONE launch,
+ * scenes[f] for frames[f], the band-set layout and out_frame_stride rules of
+ * geo_render_band_set_frames.  Frame f's bytes are those of geo_render_band_set
+ * with frames[f] and scenes[f]; with geo_set_disk_shift the hits are shaded.
+ * Every scene carries GEO_FLAG_DISK and GEO_MODE_DIRECT, with
+ * GEO_FLAG_DEFER_STEPS at most, and the scenes may differ in r_obs only (the
+ * same integration kind), else GEO_EINVAL.  GEO_FLAG_DISK's rules hold for
+ * every frame's scene: rs == 0, or r_obs > rs and rs < r_in; r_out < sphere_r
+ * and r_obs < sphere_r; with the shift set and rs > 0, r_in > 1.5 rs
+ * (GEO_EINVAL; GEO_ESTATE when no disk is set).  Colour only: a buffer armed by
+ * geo_disk_hits_next_render or geo_disk_shift_next_render is consumed and the
+ * call returns GEO_EINVAL.  A refused call launches nothing and writes nothing.
+ * The executed steps of all frames go to steps_total or, with
+ * GEO_FLAG_DEFER_STEPS, to the context's accumulator; geo_time_next_render and
+ * the dispatch order work as for the other batches (frame 0 records the tile
+ * costs).  One scene for every frame: pass copies.  Asynchronous on `stream`. */
+int geo_render_disk_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                          uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                          unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

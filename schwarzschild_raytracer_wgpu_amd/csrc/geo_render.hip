@@ -896,6 +896,149 @@ __global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderA
     }
 }
 
+// ---- geo_render_disk_batch: up to kMaxBatchFrames disk frames in one launch --
+// The two kernels above with the frame in blockIdx.z (its output a.out_frame_px
+// pixels after the last frame's), colour only, on the same wave-block grid.
+// RenderArgs and FrameBatch<kMaxBatchFrames> leave no room in the 4 KiB of
+// kernel arguments for eight frames' disk constants, so the batch has a
+// per-frame struct of its own: FrameK without what no disk kernel reads
+// (display_to_movement, which only geo::camera_consts reads on the host, and
+// three of psi_factor_and_position's four floats), the frame's scene constants,
+// and the parts of geo::DiskConsts and geo::DiskShift that change with the
+// frame: N, ex and ey with its central_to_uv, u_lo and u_hi with its scale, sb
+// and ih with its r_obs and det M2.  The host fills them with the one-frame
+// launch's geo::disk_consts and geo::disk_shift_consts, so a batch frame is the
+// one-frame render of that frame bit for bit.
+struct DiskFrameK {
+    float movement_to_central[16];
+    float central_to_uv[16];
+    float psi;  // psi_factor_and_position[0]
+    geo::CameraConsts cam;
+    float kt;
+    geo::PixelConsts k;
+    float N[3], ex[3], ey[3];
+    float u_lo, u_hi;
+    float sb, ih;  // shaded batches (zero otherwise)
+};
+struct DiskBatchArgs {
+    DiskFrameK f[kMaxBatchFrames];
+    float r_in, r_out, inv_dr, inv_step;  // geo::DiskConsts, batch-uniform
+    const uint32_t* tex;
+    float tex_w256, tex_h256;
+    uint32_t tex_pitch_b, tex_bytes;
+    float gain;  // geo::DiskShift, batch-uniform
+    uint32_t exponent;
+};
+
+// Launch geometry: the one-frame disk render's, one wave per workgroup on the
+// 1-D wave-block grid, with the frame in grid.z.  The plain batch's 32 x 8-pixel
+// workgroups of four waves on a 2-D grid (the A/B variant GEO_DISK_BATCH_TILES)
+// were measured against it.
+#if defined(GEO_DISK_BATCH_TILES)  // A/B variant
+constexpr bool kDiskBatchTiles = true;
+#else
+constexpr bool kDiskBatchTiles = false;
+#endif
+
+// SHIFT: the shaded batch (geo_set_disk_shift).  One template: no kernel that
+// existed before shares a body with it.
+template <int KIND, bool SHIFT>
+__global__ __launch_bounds__(kDiskBatchTiles ? kBlock : 64) void geo_render_disk_batch_kernel(const RenderArgs a,
+                                                                                            const DiskBatchArgs db) {
+    const uint32_t z = blockIdx.z;
+    const DiskFrameK& f = db.f[z];
+    const size_t obase = (size_t)z * a.out_frame_px;
+    uint32_t pos, wave;
+    if constexpr (kDiskBatchTiles) {
+        pos = blockIdx.y * a.tiles_x + blockIdx.x;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
+    } else {
+        const uint32_t L = blockIdx.x;
+        pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
+        wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+        if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    }
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    uint32_t steps = 0;
+    if (px < a.width && ly < a.nrows && py < a.height) {
+        float c2x, c2y, c2z, g_obs = 0.0f;
+        if constexpr (SHIFT)
+            geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
+        else
+            geo::pixel_central_dir(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
+        geo::DiskConsts dk;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            dk.N[i] = f.N[i];
+            dk.ex[i] = f.ex[i];
+            dk.ey[i] = f.ey[i];
+        }
+        dk.r_in = db.r_in;
+        dk.r_out = db.r_out;
+        dk.inv_dr = db.inv_dr;
+        dk.u_lo = f.u_lo;
+        dk.u_hi = f.u_hi;
+        dk.inv_step = db.inv_step;
+        const geo::PixelConsts& k = f.k;
+        geo::DiskRay dr;
+        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const size_t o = obase + (size_t)ly * a.width + px;
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
+                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
+                                  db.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
+        };
+        if constexpr (SHIFT) {
+            geo::DiskShift sk;
+            sk.sb = f.sb;
+            sk.ih = f.ih;
+            sk.gain = db.gain;
+            sk.exponent = db.exponent;
+            geo::DiskShiftRay sr;
+            geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
+            a.out_rgba[o] = geo::disk_shade_shift(dk, k, dr, sk, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
+        } else {
+            a.out_rgba[o] = geo::disk_shade(dk, k, dr, Uk, steps, ang, base, dsample, nullptr);
+        }
+    }
+    // (every lane of the wave is active again here, as in geo_render_kernel)
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1810,6 +1953,12 @@ static int launch_disk_shift(int kind, const RenderArgs& a, const FrameK& fk, co
                              const DiskShiftArgs& sh, uint32_t tiles_x, uint32_t tiles_y, hipStream_t s,
                              hipEvent_t done, hipEvent_t t_start, hipEvent_t t_stop);
 
+// The batched disk launch (geo_render_disk_batch_kernel), likewise defined and
+// instantiated at the end of this file.
+static int launch_disk_batch(int kind, bool shift, const RenderArgs& a, const DiskBatchArgs& db, uint32_t nframes,
+                             uint32_t tiles_x, uint32_t tiles_y, hipStream_t s, hipEvent_t done, hipEvent_t t_start,
+                             hipEvent_t t_stop);
+
 // The order buffers hold at least n tiles (both orders, the costs, the class
 // histograms).  Growing them waits for the context's renders and rebuilds,
 // and forgets the learned order.
@@ -1859,8 +2008,10 @@ static int invalid_call(geo_ctx* c) {
 // out_frame_stride bytes after frame f - 1's (a batch draws colour only).
 // scene_per_frame: `scene` points at nframes scenes, frame f's at scene[f]
 // (they may differ in r_obs only); otherwise one scene for every frame.
+// disk_batch: geo_render_disk_batch (GEO_FLAG_DISK scenes, any nframes, through
+// the batched disk kernel); the other entry points draw a disk frame alone.
 static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, size_t out_frame_stride,
-                       const geo_scene* scene, bool scene_per_frame, bool allow_disk, uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                       const geo_scene* scene, bool scene_per_frame, bool allow_disk, bool disk_batch, uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
                        uint32_t band_rows, uint32_t band_stride, uint8_t* out_rgba8, uint8_t* out_mask,
                        float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, void* stream) {
     // geo_time_next_render's events belong to this render alone, on every
@@ -1879,11 +2030,14 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
                           GEO_FLAG_DISK)) != 0)
         return GEO_EINVAL;
-    // GEO_FLAG_DISK: the one-frame entry points, direct mode, DEFER_STEPS at most
+    // GEO_FLAG_DISK: the one-frame entry points and geo_render_disk_batch, direct mode, DEFER_STEPS at most
     const bool disk = (scene->flags & GEO_FLAG_DISK) != 0;
     if (disk && (!allow_disk || scene->mode != GEO_MODE_DIRECT ||
                  (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0))
         return GEO_EINVAL;
+    // geo_render_disk_batch draws disk scenes only, and colour only: an armed
+    // per-pixel buffer (consumed above) refuses the call
+    if (disk_batch && (!disk || out_hits || out_g)) return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
         return GEO_EINVAL;
@@ -1934,6 +2088,8 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
                 !(si.r_obs > 0.0f))
                 return GEO_EINVAL;
         }
+        // GEO_FLAG_DISK's rules for this frame's observer (frame 0's above)
+        if (disk && i > 0 && (!(si.rs == 0.0f || si.r_obs > si.rs) || !(si.r_obs < si.sphere_r))) return GEO_EINVAL;
         pk[i] = geo::make_consts(si.rs, si.sphere_r, si.r_obs, si.step, si.max_steps, si.tol);
         if (geo::geodesic_kind(pk[i]) != geo::geodesic_kind(pk[0])) return GEO_EINVAL;
     }
@@ -2096,7 +2252,53 @@ static int render_impl(geo_ctx* c, const geo_frame* frames, uint32_t nframes, si
     }
     // (the disk launch last, so that its kernels are instantiated, and laid out
     // in the code object, after every kernel of the plain paths)
-    if (disk) {
+    if (disk && disk_batch) {
+        // every frame's constants by the one-frame launch's own functions
+        DiskBatchArgs db;
+        std::memset(&db, 0, sizeof(db));
+        for (uint32_t i = 0; i < nframes; ++i) {
+            const geo_scene& si = scene_per_frame ? scene[i] : *scene;
+            DiskFrameK& f = db.f[i];
+            geo::DiskConsts dk;
+            if (!geo::disk_consts(frames[i].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out,
+                                  pk[i], &dk))
+                return GEO_EINVAL;
+            std::memcpy(f.movement_to_central, fk[i].frame.movement_to_central, sizeof(f.movement_to_central));
+            std::memcpy(f.central_to_uv, fk[i].frame.central_to_uv, sizeof(f.central_to_uv));
+            f.psi = fk[i].frame.psi_factor_and_position[0];
+            f.cam = fk[i].cam;
+            f.kt = fk[i].kt;
+            f.k = pk[i];
+            for (int j = 0; j < 3; ++j) {
+                f.N[j] = dk.N[j];
+                f.ex[j] = dk.ex[j];
+                f.ey[j] = dk.ey[j];
+            }
+            f.u_lo = dk.u_lo;
+            f.u_hi = dk.u_hi;
+            if (c->shift_set) {
+                const geo::DiskShift sk = geo::disk_shift_consts(frames[i].central_to_uv, si.rs, si.r_obs,
+                                                                 c->shift.spin, c->shift.exponent, c->shift.gain);
+                f.sb = sk.sb;
+                f.ih = sk.ih;
+                db.gain = sk.gain;
+                db.exponent = sk.exponent;
+            }
+            if (i == 0) {  // (the same for every frame: the disk, and the scenes' step)
+                db.r_in = dk.r_in;
+                db.r_out = dk.r_out;
+                db.inv_dr = dk.inv_dr;
+                db.inv_step = dk.inv_step;
+            }
+        }
+        db.tex = c->disk_tex;
+        db.tex_w256 = (float)c->disk_w * 256.0f;
+        db.tex_h256 = (float)c->disk_h * 256.0f;
+        db.tex_pitch_b = (c->disk_w + 2u) * 4u;
+        db.tex_bytes = c->disk_bytes;
+        st = launch_disk_batch(geo::geodesic_kind(a.k), c->shift_set, a, db, nframes, tiles_x, tiles_y, s, done,
+                               t_start, t_stop);
+    } else if (disk) {
         DiskArgs d;
         if (!geo::disk_consts(frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out, a.k,
                               &d.k))
@@ -2358,7 +2560,7 @@ int geo_render_rows(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, 
     if ((uint64_t)row0 + nrows > height || width > (1u << 20) || height > (1u << 20))
         return invalid_call(c);
     // one band covering every row (2^21 >= nrows)
-    return render_impl(c, frame, 1, 0, scene, false, true, width, height, row0, nrows, 1u << 21, 1u << 21, out_rgba8, out_mask,
+    return render_impl(c, frame, 1, 0, scene, false, true, false, width, height, row0, nrows, 1u << 21, 1u << 21, out_rgba8, out_mask,
                        out_uv, out_steps, steps_total, stream);
 }
 
@@ -2374,7 +2576,7 @@ int geo_render_bands(geo_ctx* c, const geo_frame* frame, const geo_scene* scene,
     const uint64_t last = first + (uint64_t)(nbands - 1) * band_step * band_rows;
     const uint64_t nrows = (uint64_t)nbands * band_rows;
     if (first >= height || last >= height || nrows > (1u << 20)) return invalid_call(c);
-    return render_impl(c, frame, 1, 0, scene, false, true, width, height, (uint32_t)first, (uint32_t)nrows,
+    return render_impl(c, frame, 1, 0, scene, false, true, false, width, height, (uint32_t)first, (uint32_t)nrows,
                        band_rows, band_step * band_rows, out_rgba8, out_mask, out_uv,
                        out_steps, steps_total, stream);
 }
@@ -2398,7 +2600,7 @@ int geo_render_band_set(geo_ctx* c, const geo_frame* frame, const geo_scene* sce
                         unsigned long long* steps_total, void* stream) {
     if (!c || !frame || !scene || !out_rgba8 || !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frame, 1, 0, scene, false, true, width, height, row0, nbands * band_rows, band_rows, row_stride,
+    return render_impl(c, frame, 1, 0, scene, false, true, false, width, height, row0, nbands * band_rows, band_rows, row_stride,
                        out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
 }
 
@@ -2409,7 +2611,7 @@ int geo_render_band_set_frames(geo_ctx* c, const geo_frame* frames, uint32_t nfr
     if (!c || !frames || !scene || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
         !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frames, nframes, out_frame_stride, scene, false, false, width, height, row0, nbands * band_rows,
+    return render_impl(c, frames, nframes, out_frame_stride, scene, false, false, false, width, height, row0, nbands * band_rows,
                        band_rows, row_stride, out_rgba8, nullptr, nullptr, nullptr, steps_total, stream);
 }
 
@@ -2420,8 +2622,20 @@ int geo_render_band_set_batch(geo_ctx* c, const geo_frame* frames, const geo_sce
     if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
         !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
         return invalid_call(c);
-    return render_impl(c, frames, nframes, out_frame_stride, scenes, true, false, width, height, row0, nbands * band_rows,
+    return render_impl(c, frames, nframes, out_frame_stride, scenes, true, false, false, width, height, row0, nbands * band_rows,
                        band_rows, row_stride, out_rgba8, nullptr, nullptr, nullptr, steps_total, stream);
+}
+
+int geo_render_disk_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                          uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                          uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                          unsigned long long* steps_total, void* stream) {
+    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
+        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
+        return invalid_call(c);
+    return render_impl(c, frames, nframes, out_frame_stride, scenes, true, true, true, width, height, row0,
+                       nbands * band_rows, band_rows, row_stride, out_rgba8, nullptr, nullptr, nullptr, steps_total,
+                       stream);
 }
 
 }  // extern "C"
@@ -2433,5 +2647,50 @@ static int launch_disk_shift(int kind, const RenderArgs& a, const FrameK& fk, co
         case geo::kCurvedOut: return launch_disk<geo::kCurvedOut, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
         case geo::kCurvedIn: return launch_disk<geo::kCurvedIn, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
         default: return launch_disk<geo::kFlat, true>(a, fk, d, &sh, tiles_x, tiles_y, s, done, t_start, t_stop);
+    }
+}
+
+// The batched disk launch: launch_disk's loop with the frames in grid.z.  The
+// one-frame disk render's wave-block grid, not the plain batch's 32 x 8-pixel
+// workgroups: a disk wave holds more registers than a plain one, and its
+// frames are compared with one-frame launches wave for wave.
+static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) <= 4096, "kernel arguments fit 4 KiB");
+template <int KIND, bool SHIFT>
+static int launch_disk_batch_t(RenderArgs a, const DiskBatchArgs& db, uint32_t nframes, uint32_t tiles_x,
+                               uint32_t tiles_y, hipStream_t s, hipEvent_t done, hipEvent_t t_start,
+                               hipEvent_t t_stop) {
+    a.tiles_x = tiles_x;
+    const uint32_t max_ny = kDiskBatchTiles ? kMaxGridY : std::min(kMaxGridY, kMaxWaveBlockTiles / tiles_x);
+    for (uint32_t y0 = 0; y0 < tiles_y; y0 += max_ny) {
+        a.tile_y0 = y0;
+        const uint32_t ny = tiles_y - y0 < max_ny ? tiles_y - y0 : max_ny;
+        a.launch_tiles = tiles_x * ny;
+        const bool last = y0 + ny >= tiles_y;
+        hipEvent_t start = y0 == 0 ? t_start : nullptr;
+        hipEvent_t stop = last ? (t_stop ? t_stop : done) : nullptr;
+        const dim3 grid = kDiskBatchTiles ? dim3(tiles_x, ny, nframes)
+                                          : dim3(wave_block_count(a.launch_tiles), 1, nframes);
+        hipExtLaunchKernelGGL((geo_render_disk_batch_kernel<KIND, SHIFT>), grid, dim3(kDiskBatchTiles ? kBlock : 64),
+                              0, s, start, stop, 0, a, db);
+        if (hipGetLastError() != hipSuccess) return GEO_EHIP;
+    }
+    if (t_stop && hipEventRecord(done, s) != hipSuccess) return GEO_EHIP;
+    return GEO_OK;
+}
+
+static int launch_disk_batch(int kind, bool shift, const RenderArgs& a, const DiskBatchArgs& db, uint32_t nframes,
+                             uint32_t tiles_x, uint32_t tiles_y, hipStream_t s, hipEvent_t done, hipEvent_t t_start,
+                             hipEvent_t t_stop) {
+    if (shift) {
+        switch (kind) {
+            case geo::kCurvedOut: return launch_disk_batch_t<geo::kCurvedOut, true>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
+            case geo::kCurvedIn: return launch_disk_batch_t<geo::kCurvedIn, true>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
+            default: return launch_disk_batch_t<geo::kFlat, true>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
+        }
+    }
+    switch (kind) {
+        case geo::kCurvedOut: return launch_disk_batch_t<geo::kCurvedOut, false>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
+        case geo::kCurvedIn: return launch_disk_batch_t<geo::kCurvedIn, false>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
+        default: return launch_disk_batch_t<geo::kFlat, false>(a, db, nframes, tiles_x, tiles_y, s, done, t_start, t_stop);
     }
 }

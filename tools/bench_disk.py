@@ -13,9 +13,21 @@ it.
   python tools/bench_disk.py [--n 30] [--out profiles/disk_bench_cfg3.json]
   python tools/bench_disk.py --shift [--n 30] [--out profiles/disk_shift_bench_cfg3.json]
 
+  python tools/bench_disk.py --batch 8 [--n 30] [--out profiles/disk_batch_bench_cfg3.json]
+
 --shift adds the shaded disk frame (geo_set_disk_shift: spin +1, exponent 4,
 gain 1) as a third kind in the same alternation and reports it against the
 unshaded disk frame; its output file is a JSON list that every run appends to.
+
+--batch K measures the batched disk launch (geo_render_disk_batch) where it is
+used: a peer's share of the 4K frame at N = 8 (8-row bands, BandLayout rank 1 of
+8).  One launch of K disk frames alternates with K one-frame
+geo_render_band_set launches of the same frames back to back, unshaded and
+shaded, each on its own context; every sample is timed twice over, in two
+passes: by a pair of stream events around the launches (what a pipeline waits
+for: dispatch gaps included), and by geo_time_next_render pairs on the kernel
+dispatches alone (the K one-frame times added up).  Medians of --n samples;
+the ratios are per frame, batch over one-frame launches.
 """
 from __future__ import annotations
 
@@ -33,12 +45,18 @@ def main():
     p.add_argument("--n", type=int, default=30, help="timed renders of each kind (>= 20)")
     p.add_argument("--warmup", type=int, default=40, help="untimed renders of each kind first")
     p.add_argument("--shift", action="store_true", help="also time the Doppler-shaded disk frame")
+    p.add_argument("--batch", type=int, default=0, metavar="K",
+                   help="measure one launch of K disk frames against K one-frame launches (a peer's share at N = 8)")
     p.add_argument("--out")
     args = p.parse_args()
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json")
+        name = "disk_batch_bench_cfg3.json" if args.batch else (
+            "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json")
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.batch:
+        return batch_main(args)
 
     import numpy as np
     import torch
@@ -127,6 +145,123 @@ def main():
         doc.append(res)
     with open(args.out, "w") as f:
         f.write(json.dumps(doc, indent=1) + "\n")
+
+
+def batch_main(args):
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.dist import BandLayout
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent, hipEventDefault
+
+    K = args.batch
+    if not 1 <= K <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise SystemExit(f"--batch: 1 .. {_lib.GEO_MAX_BATCH_FRAMES}")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg = CONFIGS["cfg3_4k"]
+    W, H = cfg.width, cfg.height
+    obs = g.Observer(cfg.rs, cfg.fov, W, H)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg.step, cfg.max_steps,
+                         flags=_lib.GEO_FLAG_DISK)
+    L = BandLayout(H, 8, 8, 1)  # a peer's share at N = 8
+    band = (L.band_height(), L.row0(), L.cycle_rows, L.nbands())
+    packed = L.packed_rows() * W * 4
+    dev = torch.device("cuda:0")
+    out = torch.empty(K * packed, dtype=torch.uint8, device=dev)
+    sh = torch.cuda.current_stream().cuda_stream
+    frames = (_lib.GeoFrame * K)(*([frame] * K))
+    scenes = (_lib.GeoScene * K)(*([scene] * K))
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+
+    def make_ctx(shift):
+        c = g.Context(0)
+        c.set_sky(sky)
+        c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+        if shift:
+            c.set_disk_shift(1, 4, 1.0)
+        return c
+
+    lib = _lib.lib
+
+    def run_batch(c, pairs=None):
+        if pairs is not None:
+            c.time_next_render(*pairs[0])
+        _lib.check("geo_render_disk_batch", lib.geo_render_disk_batch(
+            c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
+
+    def run_singles(c, pairs=None):
+        for k in range(K):
+            if pairs is not None:
+                c.time_next_render(*pairs[k])
+            _lib.check("geo_render_band_set", lib.geo_render_band_set(
+                c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None,
+                None, None, sh))
+
+    # (each kind on its own context: the learned dispatch order is kept per context)
+    kinds = []
+    for shade in (False, True):
+        tag = "shift" if shade else "disk"
+        kinds.append((tag + "_batch", make_ctx(shade), run_batch, 1))
+        kinds.append((tag + "_single", make_ctx(shade), run_singles, K))
+    for _ in range(args.warmup):
+        for _, c, run, _ in kinds:
+            run(c)
+    torch.cuda.synchronize()
+    # pass 1: stream events around the launches
+    ev = {k: [] for k, _, _, _ in kinds}
+    for _ in range(args.n):
+        for kind, c, run, _ in kinds:
+            a, b = HipEvent(hipEventDefault), HipEvent(hipEventDefault)
+            a.record(sh)
+            run(c)
+            b.record(sh)
+            ev[kind].append((a, b))
+        torch.cuda.synchronize()  # the next sample's launches queue behind nothing
+    stream_ms = {k: np.array([a.elapsed_time(b) for a, b in v]) for k, v in ev.items()}
+    # pass 2: the kernel dispatches alone
+    ev = {k: [] for k, _, _, _ in kinds}
+    for _ in range(args.n):
+        for kind, c, run, m in kinds:
+            pairs = [(HipEvent(), HipEvent()) for _ in range(m)]
+            run(c, pairs)
+            ev[kind].append(pairs)
+        torch.cuda.synchronize()
+    disp_ms = {k: np.array([sum(a.elapsed_time(b) for a, b in pairs) for pairs in v]) for k, v in ev.items()}
+    for _, c, _, _ in kinds:
+        c.close()
+
+    def stats(ms):
+        return {"ms_per_frame_median": float(np.median(ms) / K), "ms_per_frame_min": float(ms.min() / K),
+                "ms_per_frame_iqr": float(np.subtract(*np.percentile(ms, [75, 25])) / K)}
+
+    res = {
+        "config": "cfg3_4k", "width": W, "height": H, "max_steps": cfg.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs],
+        "layout": {"world": 8, "rank": 1, "band_rows": band[0], "row0": band[1], "row_stride": band[2],
+                   "nbands": band[3], "rows": L.rows_mine()},
+        "frames_per_batch": K, "n": args.n, "warmup": args.warmup, "shift": [1, 4, 1.0],
+        "stream_events": {k: stats(v) for k, v in stream_ms.items()},
+        "dispatch_events": {k: stats(v) for k, v in disp_ms.items()},
+        "timing": "stream_events: a pair of events on the stream around one launch of K frames, or around K one-frame "
+                  "launches back to back; dispatch_events: geo_time_next_render pairs on the kernel dispatches, the K "
+                  "one-frame times added; the four kinds alternate in one process",
+    }
+    for how, ms in (("stream_events", stream_ms), ("dispatch_events", disp_ms)):
+        for tag in ("disk", "shift"):
+            res[how][tag + "_batch_over_single"] = float(np.median(ms[tag + "_batch"]) / np.median(ms[tag + "_single"]))
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
 
 
 if __name__ == "__main__":
