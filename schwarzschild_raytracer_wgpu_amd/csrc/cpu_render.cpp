@@ -1,5 +1,5 @@
 // cpu_render.cpp — geo_render_cpu (include/geo/geo_cpu.h): the per-pixel path
-// of geo_render_kernel (geo_render.hip: camera ray, aberration, geodesic,
+// of geo_render_kernel (geo_render_kernels.h: camera ray, aberration, geodesic,
 // sky UV, bilinear sample, blend) on the host cores, from the same header
 // geo_pixel.h, so its f32 sequence is the kernel's.  Built into its own
 // library, libgeo_cpu.so (__graft_entry__.build), with g++ -O2
@@ -91,7 +91,7 @@ Traced trace(const CpuJob& j, uint32_t px, uint32_t py) {
     return t;
 }
 
-// The kernel's sample_trilinear (geo_render.hip) on the host chain: levels
+// The kernel's sample_trilinear (geo_render_kernels.h) on the host chain: levels
 // floor(lambda) and the next, blended with frac(lambda) in 8 bits.
 uint32_t sample_trilinear(const CpuJob& j, float rho2, float U, float V) {
     const uint32_t q = geo::lod_q8(rho2);

@@ -7,7 +7,7 @@
 // known before the first RK4 step.  A disk hit is the integrator's u at a_k
 // (one partial RK4 step from the grid node below a_k) inside the annulus.
 //
-// Shared by the render kernel (geo_render.hip) and the CPU path
+// Shared by the render kernel (geo_render_kernels.h) and the CPU path
 // (cpu_render.cpp, geo_render_cpu_disk): the same f32 operation sequence, so
 // the two agree bit for bit.  The f32 specification:
 //   * (cos phi, sin phi) = (c2x, c2y) * rcpf_(rho)  ((1, 0) for rho = 0)

@@ -410,7 +410,7 @@ GEO_HD bool in_ballot_(uint64_t m) { return m != 0; }
 #define GEO_RARE() ((void)0)
 #endif
 
-// Diagnostic builds count the waves by the loop they take (geo_render.hip,
+// Diagnostic builds count the waves by the loop they take (geo_render_kernels.h,
 // GEO_WAVE_LOG); nothing otherwise.
 #if !defined(GEO_LOOP_COUNT)
 #define GEO_LOOP_COUNT(end_test) ((void)0)

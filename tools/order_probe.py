@@ -35,7 +35,7 @@ import schwarzschild_raytracer_wgpu_amd as g  # noqa: E402
 from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_sky  # noqa: E402
 from schwarzschild_raytracer_wgpu_amd.timing import HipEvent  # noqa: E402
 
-TW, TH, WW, WH = 32, 8, 16, 4  # tile and wave shapes (geo_render.hip)
+TW, TH, WW, WH = 32, 8, 16, 4  # tile and wave shapes (geo_render_kernels.h)
 
 
 def xcd_order(packed, rank=None, parts=None):

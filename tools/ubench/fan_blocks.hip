@@ -23,7 +23,7 @@ struct Args {
     float tw256, th256;
 };
 
-struct Quad {  // the padded sky's 2 x 2 block (geo_render.hip PaddedSkyQuad)
+struct Quad {  // the padded sky's 2 x 2 block (geo_render_kernels.h PaddedSkyQuad)
     __amdgpu_buffer_rsrc_t rsrc;
     uint32_t pitch_b;
     __device__ __forceinline__ void operator()(int ix0, int iy0, uint32_t (&t)[4]) const {

@@ -11,7 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 
-constexpr int kWords = 0x00020000;  // raw buffer resource word 3, as geo_render.hip
+constexpr int kWords = 0x00020000;  // raw buffer resource word 3, as geo_render_kernels.h
 
 __global__ __launch_bounds__(256) void read_dwordx2(const uint32_t* src, uint32_t bytes, uint32_t* out) {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(src), 0, (int)bytes, kWords);
