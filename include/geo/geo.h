@@ -56,10 +56,12 @@ extern "C" {
                                    geo_disk_hits_next_render;
                                    announced by GEO_HAS_DISK_SHIFT: geo_disk_shift,
                                    geo_set_disk_shift, geo_disk_shift_next_render;
-                                   announced by GEO_HAS_DISK_BATCH: geo_render_disk_batch) */
+                                   announced by GEO_HAS_DISK_BATCH: geo_render_disk_batch;
+                                   announced by GEO_HAS_SS4: GEO_FLAG_SS4) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
+#define GEO_HAS_SS4 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -146,6 +148,37 @@ typedef enum geo_status {
                                    _COMPOSITE.
                                    With geo_set_disk_shift the hits are shaded by their
                                    Doppler and redshift factor. */
+#define GEO_FLAG_SS4 32u        /* (a build extension, not in the reference) 2 x 2 supersampling,
+                                   resolved in the render kernel: output pixel (x, y) of the
+                                   width x height render is drawn from four samples, sample
+                                   (i, j), i, j in {0, 1}, being pixel (2x + i, 2y + j) of the
+                                   2 width x 2 height render of the same geo_frame and the same
+                                   scene without this flag, bit for bit (the camera takes the
+                                   frame and the frame size only, so the samples sit a quarter
+                                   of a pixel from the centre).  Each of R, G, B, A on its own
+                                   is (s00 + s01 + s10 + s11 + 2) >> 2 of the 8-bit values that
+                                   render writes.  steps_total (or the context's accumulator,
+                                   GEO_FLAG_DEFER_STEPS) receives the steps of every sample:
+                                   the 2 width x 2 height render's over sample rows 2r, 2r + 1
+                                   of the requested rows r.  Colour only: out_mask, out_uv and
+                                   out_steps must be NULL, and a buffer armed by
+                                   geo_disk_hits_next_render or geo_disk_shift_next_render is
+                                   consumed and refuses the call (GEO_EINVAL).
+                                   geo_render_rows / _bands / _band_set, GEO_MODE_DIRECT, the
+                                   level-0 sampler, with GEO_FLAG_DISK (shaded by
+                                   geo_set_disk_shift or not) and GEO_FLAG_DEFER_STEPS at most.
+                                   GEO_EINVAL with GEO_MODE_FAN, GEO_MODE_ADAPTIVE,
+                                   GEO_FLAG_MIPS, GEO_FLAG_COMPOSITE or GEO_FLAG_RING_F64,
+                                   through geo_render_band_set_frames / _batch and
+                                   geo_render_disk_batch, and where 2 width or 2 height
+                                   (or twice the rows of a band layout) exceeds what the call
+                                   takes as width, height and rows (2^20).  Rows and bands are
+                                   in output pixels; the tile grid (geo_set_tile_order, the
+                                   learned order, which is the supersampled render's own) is
+                                   the sample frame's, ceil(2 width / 32) x ceil(2 nrows / 8).
+                                   No buffer of samples is kept: a wave's 16 x 4 samples are
+                                   8 x 2 output pixels, resolved across its lanes
+                                   (DESIGN.md §3). */
 #define GEO_DISK_MAX_CROSSINGS 3
 #define GEO_DISK_G_MAX 16.0f    /* the largest frequency ratio a shaded hit reports
                                    (geo_set_disk_shift; csrc/geo_disk.h) */

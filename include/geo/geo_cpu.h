@@ -14,6 +14,13 @@
  * pixel's level of detail from its frame-aligned 2 x 2 quad, tracing the
  * quad partners outside the frame or the requested rows as the kernel's
  * helper lanes do; any row0 and row_step are accepted.
+ * GEO_FLAG_SS4 (geo.h) is taken by all three entry points under the device's
+ * rules (GEO_MODE_DIRECT, GEO_FLAG_DISK and GEO_FLAG_DEFER_STEPS at most, width
+ * and height at most 2^19; out_mask, out_uv, out_steps, out_hits and out_g must
+ * be NULL): output row i is frame row row0 + i row_step, its samples are rows
+ * 2 (row0 + i row_step) and the next of the 2 width x 2 height frame, traced
+ * through the same header and resolved with the kernel's integer rule;
+ * steps_total counts every sample's steps.
  */
 #ifndef GEO_GEO_CPU_H
 #define GEO_GEO_CPU_H

@@ -31,6 +31,8 @@ GEO_FLAG_COMPOSITE = 2
 GEO_FLAG_MIPS = 4
 GEO_FLAG_RING_F64 = 8
 GEO_FLAG_DISK = 16
+GEO_FLAG_SS4 = 32  # 2 x 2 supersampling, resolved in the kernel (GEO_HAS_SS4)
+GEO_HAS_SS4 = 1
 GEO_DISK_MAX_CROSSINGS = 3
 GEO_RING_X = 5e-3
 GEO_MAX_BATCH_FRAMES = 8

@@ -256,7 +256,9 @@ class Context:
 
     def render_rows(self, frame: GeoFrame, scene: GeoScene, width: int, height: int, row0: int, nrows: int,
                     out_rgba, out_mask=None, out_uv=None, out_steps=None, steps_total=None, stream=None) -> None:
-        """geo_render_rows; outputs are device tensors (rgba: nrows*width*4 u8)."""
+        """geo_render_rows; outputs are device tensors (rgba: nrows*width*4 u8).  A GEO_FLAG_SS4
+        scene (2 x 2 supersampling) draws colour only: out_mask, out_uv and out_steps stay None;
+        width, height, rows and the output are in output pixels."""
         _check_outputs(nrows, width, out_rgba, out_mask, out_uv, out_steps, steps_total)
         check("geo_render_rows", lib.geo_render_rows(
             self._h, ctypes.byref(frame), ctypes.byref(scene), width, height, row0, nrows,

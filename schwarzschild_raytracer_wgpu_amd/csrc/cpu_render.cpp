@@ -266,6 +266,38 @@ unsigned long long run_rows(const CpuJob& j, unsigned tid, unsigned nthreads) {
     return total;
 }
 
+// GEO_FLAG_SS4 rows: j is the job of the 2W x 2H sample frame (its width, its
+// camera; row0, nrows and row_step are the call's, in output rows) and out the
+// call's colour rows, j.width / 2 pixels wide.  Output row i is frame row
+// row0 + i row_step; its samples are rows 2 r and 2 r + 1 of the sample frame,
+// traced by the one-sample row loops above into a two-row buffer, then resolved
+// per channel with the kernel's rule, (s00 + s01 + s10 + s11 + 2) >> 2.
+unsigned long long run_rows_ss(const CpuJob& j, uint32_t* out, unsigned tid, unsigned nthreads) {
+    unsigned long long total = 0;
+    const uint32_t sw = j.width, ow = sw / 2u;
+    std::vector<uint32_t> pair((size_t)2u * sw);
+    CpuJob sj = j;
+    sj.rgba = pair.data();
+    sj.nrows = 2;
+    sj.row_step = 1;
+    for (uint32_t ly = tid; ly < j.nrows; ly += nthreads) {
+        sj.row0 = 2u * (j.row0 + ly * j.row_step);
+        total += run_rows(sj, 0, 1);
+        const uint32_t* s0 = pair.data();
+        const uint32_t* s1 = s0 + sw;
+        for (uint32_t x = 0; x < ow; ++x) {
+            uint32_t px = 0;
+            for (uint32_t sh = 0; sh < 32u; sh += 8u) {
+                const uint32_t sum = ((s0[2u * x] >> sh) & 255u) + ((s0[2u * x + 1u] >> sh) & 255u) +
+                                     ((s1[2u * x] >> sh) & 255u) + ((s1[2u * x + 1u] >> sh) & 255u);
+                px |= ((sum + 2u) >> 2) << sh;
+            }
+            out[(size_t)ly * ow + x] = px;
+        }
+    }
+    return total;
+}
+
 }  // namespace
 
 namespace {
@@ -288,7 +320,15 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
         return GEO_EINVAL;
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
-                          (disk ? GEO_FLAG_DISK : 0u))) != 0)
+                          (disk ? GEO_FLAG_DISK : 0u) | GEO_FLAG_SS4)) != 0)
+        return GEO_EINVAL;
+    // GEO_FLAG_SS4 (geo.h), by the device's rules: direct mode, the level-0
+    // sampler, colour only, DISK and DEFER_STEPS at most, and a sample frame of
+    // twice the size within this path's limits
+    const bool ss = (scene->flags & GEO_FLAG_SS4) != 0;
+    if (ss && (scene->mode != GEO_MODE_DIRECT ||
+               (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || out_mask || out_uv ||
+               out_steps || out_hits || out_g || width > (1u << 19) || height > (1u << 19)))
         return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
@@ -296,7 +336,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     if (disk) {
         // geo_render_rows' GEO_FLAG_DISK rules and geo_set_disk's (geo.h)
         if ((scene->flags & GEO_FLAG_DISK) == 0 || scene->mode != GEO_MODE_DIRECT ||
-            (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0)
+            (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0)
             return GEO_EINVAL;
         if (!disk_rgba8 || disk_w == 0 || disk_h == 0 || disk_w > (1u << 20) || disk_h > (1u << 20) ||
             ((uint64_t)disk_w + 2u) * ((uint64_t)disk_h + 2u) * 4u >= (1ull << 31))
@@ -333,7 +373,9 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.f = frame;
     j.s = scene;
     j.k = geo::make_consts(scene->rs, scene->sphere_r, scene->r_obs, scene->step, scene->max_steps, scene->tol);
-    j.cam = geo::camera_consts(frame->display_to_movement, frame->movement_to_central, width, height);
+    // (GEO_FLAG_SS4: the job is the 2W x 2H sample frame's, run_rows_ss)
+    const uint32_t ssf = ss ? 2u : 1u;
+    j.cam = geo::camera_consts(frame->display_to_movement, frame->movement_to_central, ssf * width, ssf * height);
     j.kt = geo::aberration_kt(frame->psi_factor_and_position[0]);
     j.sky = sky.data();
     j.sw = sky_w;
@@ -341,7 +383,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.opaque = opaque;
     j.fan = fan;
     j.n_fan = n_fan;
-    j.width = width;
+    j.width = ssf * width;
     j.row0 = row0;
     j.nrows = nrows;
     j.row_step = row_step;
@@ -350,7 +392,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.uv = out_uv;
     j.steps = out_steps;
     j.ring = ring_flag && scene->rs > 0.0f && scene->r_obs > scene->rs;
-    if (j.ring) j.band = geo::band_consts(*frame, *scene, width, height);
+    if (j.ring) j.band = geo::band_consts(*frame, *scene, width, height);  // (never with GEO_FLAG_SS4)
     j.disk = disk != nullptr;
     j.dtex = nullptr;
     j.dw = disk_w;
@@ -389,8 +431,12 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     std::vector<unsigned long long> part(n, 0);
     std::vector<std::thread> pool;
     pool.reserve(n - 1);
-    for (unsigned t = 1; t < n; ++t) pool.emplace_back([&j, &part, t, n] { part[t] = run_rows(j, t, n); });
-    part[0] = run_rows(j, 0, n);
+    uint32_t* const out = reinterpret_cast<uint32_t*>(out_rgba8);
+    const auto work = [&j, out, ss](unsigned t, unsigned nt) {
+        return ss ? run_rows_ss(j, out, t, nt) : run_rows(j, t, nt);
+    };
+    for (unsigned t = 1; t < n; ++t) pool.emplace_back([&work, &part, t, n] { part[t] = work(t, n); });
+    part[0] = work(0, n);
     for (auto& th : pool) th.join();
     unsigned long long total = 0;
     for (unsigned long long p : part) total += p;
@@ -430,7 +476,9 @@ extern "C" int geo_render_cpu_disk_shift(const geo_frame* frame, const geo_scene
                                          const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
                                          uint32_t disk_h, float* out_hits, const geo_disk_shift* shift, float* out_g) {
     if (!disk) return GEO_EINVAL;
+    // (GEO_FLAG_SS4 is colour only: out_g refuses the call whether it would be written or not)
+    const bool ss = scene && (scene->flags & GEO_FLAG_SS4) != 0;
     return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
-                           disk_h, out_hits, shift, shift ? out_g : nullptr);
+                           disk_h, out_hits, shift, shift || ss ? out_g : nullptr);
 }

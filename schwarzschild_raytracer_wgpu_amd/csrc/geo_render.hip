@@ -669,6 +669,7 @@ struct RenderWork {
     float* out_hits;  // geo_disk_hits_next_render's buffer, geo_disk_shift_next_render's
     float* out_g;
     bool disk, ring_flag, mips, adaptive, defer;  // what the scene asks for (check_scene)
+    bool ss;  // GEO_FLAG_SS4: the kernels' frame is the sample frame, twice the call's in width, height and rows
     bool ring;                                    // ring_flag and a capture orbit to draw (fill_frames)
     FrameK fk[kMaxBatchFrames];
     geo::PixelConsts pk[kMaxBatchFrames];
@@ -686,12 +687,24 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
         return GEO_EINVAL;
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
-                          GEO_FLAG_DISK)) != 0)
+                          GEO_FLAG_DISK | GEO_FLAG_SS4)) != 0)
+        return GEO_EINVAL;
+    // GEO_FLAG_SS4 (every rule here, where the bit was refused as an unknown
+    // one before: a call that breaks an older rule too keeps its status): the
+    // one-frame entry points (the ones that draw a disk frame alone), direct
+    // mode, the level-0 sampler, colour only (an armed hit or g buffer,
+    // consumed by render_impl, refuses the call), DISK and DEFER_STEPS at
+    // most, and a sample frame of twice the size that the entry points take
+    w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
+    if (w.ss && (!rc.allow_disk || rc.disk_batch || rc.nframes != 1 || scene->mode != GEO_MODE_DIRECT ||
+                 (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
+                 rc.out_uv || rc.out_steps || w.out_hits || w.out_g || rc.width > (1u << 19) ||
+                 rc.height > (1u << 19)))
         return GEO_EINVAL;
     // GEO_FLAG_DISK: the one-frame entry points and geo_render_disk_batch, direct mode, DEFER_STEPS at most
     w.disk = (scene->flags & GEO_FLAG_DISK) != 0;
     if (w.disk && (!rc.allow_disk || scene->mode != GEO_MODE_DIRECT ||
-                   (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0))
+                   (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0))
         return GEO_EINVAL;
     // geo_render_disk_batch draws disk scenes only, and colour only: an armed
     // per-pixel buffer (consumed by render_impl) refuses the call
@@ -736,7 +749,10 @@ static int fill_frames(const RenderCall& rc, RenderWork& w) {
     for (uint32_t i = 0; i < rc.nframes; ++i) {
         const geo_frame& fr = rc.frames[i];
         std::memcpy(&w.fk[i].frame, &fr, sizeof(geo_frame));
-        w.fk[i].cam = geo::camera_consts(fr.display_to_movement, fr.movement_to_central, rc.width, rc.height);
+        // (GEO_FLAG_SS4: the camera of the 2W x 2H sample frame; it takes the frame and the size only)
+        const uint32_t ssf = w.ss ? 2u : 1u;
+        w.fk[i].cam = geo::camera_consts(fr.display_to_movement, fr.movement_to_central, ssf * rc.width,
+                                         ssf * rc.height);
         w.fk[i].kt = geo::aberration_kt(fr.psi_factor_and_position[0]);
         const geo_scene& si = rc.scene_per_frame ? scene[i] : *scene;
         if (i > 0 && rc.scene_per_frame) {
@@ -773,18 +789,23 @@ static void fill_args(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     a.wave_log = c->wave_log;
 #endif
     a.k = w.pk[0];
-    a.width = rc.width;
-    a.height = rc.height;
-    a.row0 = rc.row0;
-    a.nrows = rc.nrows;
-    a.band_rows = rc.band_rows;
+    // GEO_FLAG_SS4: the sample frame's sizes and rows (twice the call's; the
+    // output's pitch rides in SsArgs).  band_magic stays the call's
+    // band_rows': the SS kernels take the band index on output rows, where
+    // band_rows_magic is exact.
+    const uint32_t ssf = w.ss ? 2u : 1u;
+    a.width = ssf * rc.width;
+    a.height = ssf * rc.height;
+    a.row0 = ssf * rc.row0;
+    a.nrows = ssf * rc.nrows;
+    a.band_rows = ssf * rc.band_rows;
     a.band_magic = band_rows_magic(rc.band_rows);
-    a.band_stride = rc.band_stride;
+    a.band_stride = ssf * rc.band_stride;
     a.sky_opaque = c->sky_opaque ? 1u : 0u;
     a.composite = (rc.scene->flags & GEO_FLAG_COMPOSITE) ? 1u : 0u;
-    w.p.tiles_x = (rc.width + kTileW - 1) / kTileW;
+    w.p.tiles_x = (a.width + kTileW - 1) / kTileW;
     const uint32_t tile_h = kTileH * lane_rows(rc.scene->mode, w.mips);
-    w.p.tiles_y = (rc.nrows + tile_h - 1) / tile_h;
+    w.p.tiles_y = (a.nrows + tile_h - 1) / tile_h;
     a.sky = c->sky;
     a.sky_w = c->sky_w;
     a.sky_h = c->sky_h;
@@ -846,9 +867,11 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
         return GEO_OK;
     }
     if (c->dispatch_mode != GEO_DISPATCH_LONGEST_FIRST) return GEO_OK;
-    // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost more)
+    // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost
+    // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
-                             (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u), tiles_x * tiles_y};
+                             (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u),
+                             tiles_x * tiles_y};
     if (!c->learn_valid || std::memcmp(key, c->learn_key, sizeof(key)) != 0) {
         std::memcpy(c->learn_key, key, sizeof(key));
         c->learn_valid = true;
@@ -932,6 +955,52 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
     });
 }
 
+// Stage 5, a GEO_FLAG_SS4 frame: the plain frame, the disk frame or the shifted
+// disk frame, the disk's constants as launch_disk_frame derives them (they do
+// not depend on the resolution).
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(SsArgs<kSsDiskShift>) <= 4096,
+              "kernel arguments fit 4 KiB");
+static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    SsArgs<kSsDiskShift> x;
+    x.out_width = rc.width;
+    if (w.disk) {
+        if (!geo::disk_consts(rc.frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out,
+                              w.a.k, &x.d.k))
+            return GEO_EINVAL;
+        fill_disk_tex(c, x.d);
+        x.d.out_hits = nullptr;
+        if (c->shift_set) {
+            x.sh.k = geo::disk_shift_consts(rc.frames[0].central_to_uv, rc.scene->rs, rc.scene->r_obs, c->shift.spin,
+                                            c->shift.exponent, c->shift.gain);
+            x.sh.out_g = nullptr;
+        }
+    }
+    FrameBatch<1> fb;
+    fb.f[0] = w.fk[0];
+    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
+                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+            const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
+            if (!w.disk) {
+                SsArgs<kSsPlain> xp;
+                xp.out_width = x.out_width;
+                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsPlain>), grid, block, 0, w.p.s, start, stop, 0, la,
+                                      fb, xp);
+            } else if (!c->shift_set) {
+                SsArgs<kSsDisk> xd;
+                xd.out_width = x.out_width;
+                xd.d = x.d;
+                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsDisk>), grid, block, 0, w.p.s, start, stop, 0, la,
+                                      fb, xd);
+            } else {
+                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsDiskShift>), grid, block, 0, w.p.s, start, stop, 0,
+                                      la, fb, x);
+            }
+        });
+    });
+}
+
 // Stage 5, geo_render_disk_batch: every frame's constants by the one-frame
 // launch's own functions.
 static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
@@ -980,6 +1049,7 @@ static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const Rend
 
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    if (w.ss) return launch_ss_frame(c, rc, w);
     if (w.disk) return rc.disk_batch ? launch_disk_frames(c, rc, w) : launch_disk_frame(c, rc, w);
     if (rc.scene->mode == GEO_MODE_FAN) return launch_fan(c, rc, w);
     geo::BandConsts band_k;  // (one frame; a batch derives its frames' constants on the device)

@@ -1036,6 +1036,150 @@ __global__ __launch_bounds__(kDiskBatchTiles ? kBlock : 64) void geo_render_disk
     }
 }
 
+// ---- GEO_FLAG_SS4: 2 x 2 supersampling, resolved in the kernel -----------
+// The one-frame direct-mode kernels above with a lane per SAMPLE: RenderArgs
+// describes the sample frame (width, height, row0, nrows, band_rows and
+// band_stride are twice the call's; f.cam is geo::camera_consts at twice the
+// size), so a lane traces and shades pixel (px, py) of the 2W x 2H render
+// exactly as its one-sample sibling does, keeps the colour in a register, and
+// the wave's 16 x 4 samples are resolved to 8 x 2 output pixels across its
+// lanes.  Kernels of their own (VAR: the plain frame, the disk frame, the
+// shifted disk frame) with their own further argument: the kernels that
+// existed before keep their code, arguments and resource records.
+constexpr int kSsPlain = 0, kSsDisk = 1, kSsDiskShift = 2;
+template <int VAR>
+struct SsArgs {
+    uint32_t out_width;  // the output's pitch in pixels (RenderArgs::width is the sample frame's, twice it)
+};
+template <>
+struct SsArgs<kSsDisk> {
+    uint32_t out_width;
+    DiskArgs d;
+};
+template <>
+struct SsArgs<kSsDiskShift> {
+    uint32_t out_width;
+    DiskArgs d;
+    DiskShiftArgs sh;
+};
+
+// lane_xor1 / lane_xor16 on integers: a sample's x and y partners in its
+// output pixel's 2 x 2 quad.
+__device__ __forceinline__ uint32_t lane_xor1_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t lane_xor16_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
+}
+
+// The box resolve of an output pixel's four samples (lanes l, l ^ 1, l ^ 16,
+// l ^ 17), each 8-bit channel on its own: (s00 + s01 + s10 + s11 + 2) >> 2.
+// Two channels per register: c & 0x00FF00FF holds R and B, (c >> 8) &
+// 0x00FF00FF G and A, in 16-bit fields; a field's sum over four samples is at
+// most 1020 (1022 with the rounding term), so it never carries into its
+// neighbour.  Every lane of the wave must be active: a cross-lane read from an
+// inactive lane returns nothing useful.
+__device__ __forceinline__ uint32_t ss_resolve(uint32_t c) {
+    uint32_t rb = c & 0x00FF00FFu, ga = (c >> 8) & 0x00FF00FFu;
+    rb += lane_xor1_u32(rb);
+    ga += lane_xor1_u32(ga);
+    rb += lane_xor16_u32(rb);
+    ga += lane_xor16_u32(ga);
+    rb = ((rb + 0x00020002u) >> 2) & 0x00FF00FFu;
+    ga = ((ga + 0x00020002u) >> 2) & 0x00FF00FFu;
+    return rb | (ga << 8);
+}
+
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                           const SsArgs<VAR> x) {
+    const FrameK& f = fb.f[0];
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
+    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // (px, ly): the lane's sample in the 2W x 2 nrows grid; py its row of the
+    // 2H sample frame.  The band index is taken on output rows (wl0 / 2 over
+    // the call's band_rows: band_magic is that divisor's, within the range
+    // band_rows_magic is exact on); a.band_rows, a.band_stride and a.row0 are
+    // in sample rows.  Bands are multiples of 16 sample rows, so the wave's
+    // four rows lie in one.
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    // In the frame or out of it, the four samples of an output pixel go
+    // together: a.width, a.nrows and a.height are even (twice the call's),
+    // px and px ^ 1 differ in bit 0 only, and so do ly and ly ^ 1 and, with
+    // them, py and its partner (wl0 is a multiple of 4; a.row0, a.band_stride
+    // and a.band_rows are even, so py - (ly - wl0) is even and py's bit 0 is
+    // ly's).  Lanes l ^ 1 and l ^ 16 hold samples (px ^ 1, ly) and (px, ly ^ 1).
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // the sample's colour, kept in a register
+    if (in_frame) {
+        float c2x, c2y, c2z, g_obs = 0.0f;
+        if constexpr (VAR == kSsDiskShift)
+            geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px,
+                                     py, &c2x, &c2y, &c2z, &g_obs);
+        else
+            geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                                   &c2x, &c2y, &c2z);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        if constexpr (VAR == kSsPlain) {
+            const float lam = pixel_lambda<GEO_MODE_DIRECT, KIND>(a, a.k, st, ct, rct, &steps);
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+            colour = bh ? geo::kBlackRGBA
+                        : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        } else {
+            const DiskArgs& d = x.d;
+            geo::DiskRay dr;
+            geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+            float Uk[geo::kDiskMaxCrossings];
+            const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+            const float lam = geo::kPi2 - ang;
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+            const uint32_t base = bh ? geo::kBlackRGBA
+                                     : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+            const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0,
+                                                                        (int)d.tex_bytes, kBufferRsrcWord3),
+                                      d.tex_pitch_b};
+            const auto dsample = [&](float Ud, float Vd) {
+                return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
+            };
+            if constexpr (VAR == kSsDiskShift) {
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(d.k, x.sh.k, dr, ct, g_obs, &sr);
+                colour = geo::disk_shade_shift(d.k, a.k, dr, x.sh.k, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
+            } else {
+                colour = geo::disk_shade(d.k, a.k, dr, Uk, steps, ang, base, dsample, nullptr);
+            }
+        }
+    }
+    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
+    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
+    // of the frame resolves four zeros and is not stored.
+    const uint32_t resolved = ss_resolve(colour);
+    if (in_frame && (lane & 0x11u) == 0u) a.out_rgba[(size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
+    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1446,6 +1590,15 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_batch_kernel<geo::kCurvedOut, false>;
     (void)geo_render_disk_batch_kernel<geo::kCurvedIn, false>;
     (void)geo_render_disk_batch_kernel<geo::kFlat, false>;
+    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsPlain>;
+    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsPlain>;
+    (void)geo_render_ss_kernel<geo::kFlat, kSsPlain>;
+    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsDisk>;
+    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsDisk>;
+    (void)geo_render_ss_kernel<geo::kFlat, kSsDisk>;
+    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsDiskShift>;
+    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsDiskShift>;
+    (void)geo_render_ss_kernel<geo::kFlat, kSsDiskShift>;
 }
 
 }  // namespace

@@ -7,14 +7,16 @@ the present step of the absent wgpu_renderer loop.
         [--sky eso0932a.jpg --planet world_8k.png --clouds transparent_clouds.png]
         [--frames 60 --orbit 3.2] [--mipmaps] [--fan]
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
-        [--disk-shift SPIN EXP GAIN]
+        [--disk-shift SPIN EXP GAIN] [--ss]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
 images) instead of the reference's scene; --cpu renders it with the CPU path
 (libgeo_cpu.so, the same bytes, no GPU needed).  --disk-shift SPIN EXP GAIN
 shades the disk by its Doppler and redshift factor g (geo_set_disk_shift:
-matter orbiting about SPIN * normal, colours times GAIN * g**EXP).
+matter orbiting about SPIN * normal, colours times GAIN * g**EXP).  --ss
+draws the disk frame 2 x 2 supersampled (GEO_FLAG_SS4: four rays per pixel,
+resolved in the kernel), on the GPU or with --cpu.
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -46,7 +48,8 @@ def disk_frame(args):
     obs.set_position(*args.pos)
     obs.set_camera(*args.camera)
     frame = obs.calc_transformation_pipeline()
-    scene = g.make_scene(1.0, 50.0, obs.get_radial_position(), math.pi / 100, 2048, flags=_lib.GEO_FLAG_DISK)
+    scene = g.make_scene(1.0, 50.0, obs.get_radial_position(), math.pi / 100, 2048,
+                         flags=_lib.GEO_FLAG_DISK | (_lib.GEO_FLAG_SS4 if args.ss else 0))
     sky = imageio.load_texture(args.sky) if args.sky else make_sky("equirect", (2048, 1024))
     tex = make_disk_texture((1024, 128))
     r_in, r_out = args.disk
@@ -87,7 +90,8 @@ def disk_frame(args):
         Image.fromarray(imageio.frame_to_host(rgba, w, h)[..., :3].copy(), "RGB").save(args.out, quality=88)
     else:
         imageio.save_png(args.out, rgba, w, h)
-    print(f"wrote {args.out} ({w}x{h}, thin disk {r_in}..{r_out}, {'CPU path' if args.cpu else 'GPU'})")
+    print(f"wrote {args.out} ({w}x{h}{', 2x2 supersampled' if args.ss else ''}, thin disk {r_in}..{r_out}, "
+          f"{'CPU path' if args.cpu else 'GPU'})")
 
 
 def main():
@@ -111,12 +115,15 @@ def main():
     p.add_argument("--disk-shift", type=float, nargs=3, metavar=("SPIN", "EXP", "GAIN"),
                    help="with --disk: Doppler and redshift shading (geo_set_disk_shift)")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (geo_render_cpu_disk_shift)")
+    p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
     p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
     p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
     p.add_argument("--fov", type=float, default=math.pi / 2, help="with --disk")
     args = p.parse_args()
     if args.disk:
         return disk_frame(args)
+    if args.ss:
+        p.error("--ss goes with --disk (the scene's spheres are composited, which GEO_FLAG_SS4 refuses)")
 
     import torch
 
