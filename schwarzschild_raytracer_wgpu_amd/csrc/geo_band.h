@@ -54,10 +54,7 @@ struct BandConsts {
 };
 
 // The band test on the f32 draw's cos(theta) (central_rho).
-#if !defined(GEO_BAND_X)  // (A/B variants only; the specification is GEO_RING_X)
-#define GEO_BAND_X GEO_RING_X
-#endif
-GEO_HD bool in_band(float kx, float ct) { return __builtin_fabsf(kx * ct - 1.0f) < GEO_BAND_X; }
+GEO_HD bool in_band(float kx, float ct) { return __builtin_fabsf(kx * ct - 1.0f) < GEO_RING_X; }
 
 // kx = r / (E b_c) rounded once: the band test's factor (rs > 0, r_obs > rs).
 GEO_HD float band_kx(float rs, float r_obs) {

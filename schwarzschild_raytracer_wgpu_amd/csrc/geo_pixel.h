@@ -1266,8 +1266,8 @@ GEO_HD void pad_sky(const uint8_t* rgba8, uint32_t tw, uint32_t th, uint32_t* ds
     }
 }
 
-// Level 0 of the padded sky again as row pairs (the device's bilinear reads
-// this copy): padded texels (x, y) and (x, y + 1) side by side in 8 bytes,
+// Level 0 of the padded sky again as row pairs (host code only: no kernel
+// reads this layout, geo_render_kernels.h): padded texels (x, y) and (x, y + 1) side by side in 8 bytes,
 // rows y = 0 .. th, so the quad at padded (x, y) is the 16 bytes at
 // 2 ((y (tw + 2) + x)) texels: one 16-byte load, one 128-B line.  pad: the
 // padded level (pad_sky), dst: 2 (th + 1) (tw + 2) texels.

@@ -192,11 +192,6 @@ int geo_set_sky(geo_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h) {
         total += ((uint64_t)lw[l] + 2u) * ((uint64_t)lh[l] + 2u) * 4u;
         if (total >= (1ull << 31)) return GEO_EINVAL;
     }
-    const uint64_t pairs_off = total;  // kSkyPairs: level 0's row pairs after the chain
-    if (kSkyPairs) {
-        total += ((uint64_t)w + 2u) * ((uint64_t)h + 1u) * 8u;
-        if (total >= (1ull << 31)) return GEO_EINVAL;
-    }
     DeviceGuard g(c->device);
     if (!g.ok) return GEO_EHIP;
     // the chain on the host: level 0 = the texture, level l + 1 = the 2 x 2
@@ -212,7 +207,6 @@ int geo_set_sky(geo_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h) {
         }
         geo::pad_sky(reinterpret_cast<const uint8_t*>(lvl.data()), lw[l], lh[l], pad.data() + loff[l] / 4u);
     }
-    if (kSkyPairs) geo::pair_sky_rows(pad.data(), w, h, pad.data() + pairs_off / 4u);
     // Renders of this context still running on any of the caller's streams
     // (non-blocking ones do not order against a blocking copy) may be reading
     // the current sky: let them finish before it is overwritten or freed.  A
@@ -239,7 +233,6 @@ int geo_set_sky(geo_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h) {
     c->sky_w = w;
     c->sky_h = h;
     c->sky_total_bytes = (uint32_t)total;
-    c->sky_pairs_off = (uint32_t)pairs_off;
     for (int l = 0; l < geo_ctx::kSkyLevels; ++l) {
         c->sky_lvl_w[l] = lw[l];
         c->sky_lvl_h[l] = lh[l];
@@ -490,10 +483,7 @@ static int launch_tiles(const RenderArgs& a, const FrameBatch<NF>& fb, uint32_t 
         return launch_split(a, p, wb ? wave_block_max_ny(p.tiles_x) : kMaxGridY,
                             [&](const RenderArgs& la, uint32_t ny, hipEvent_t start, hipEvent_t stop) {
             dim3 grid(p.tiles_x, ny, nframes), block(kBlock);
-            if (wb)
-                grid = dim3(wave_block_count(la.launch_tiles)), block = dim3(64);
-            else if (MODE == GEO_MODE_FAN && kFanPersist && !mips)
-                grid = dim3(std::min(la.launch_tiles, la.persist_blocks), 1, nframes);
+            if (wb) grid = dim3(wave_block_count(la.launch_tiles)), block = dim3(64);
             hipExtLaunchKernelGGL(kernel, grid, block, 0, p.s, start, stop, 0, la, fb, bk);
         });
     };
@@ -502,7 +492,7 @@ static int launch_tiles(const RenderArgs& a, const FrameBatch<NF>& fb, uint32_t 
             if constexpr (NF == 1) {
                 BandArg<true> bk;
                 bk.k = *band;
-                return run(geo_render_kernel<MODE, KIND, false, 1, true>, kRingWaveBlocks, bk);
+                return run(geo_render_kernel<MODE, KIND, false, 1, true>, wave_blocks(MODE, false, 1, true), bk);
             } else {  // fb.ring_kx, the constants derived per wave
                 return run(geo_render_kernel<MODE, KIND, false, NF, true>, false, BandArg<false>{});
             }
@@ -582,11 +572,9 @@ static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) <= 4096, "kernel argume
 template <int KIND>
 static int launch_disk_batch(const RenderArgs& a, const DiskBatchArgs& db, uint32_t nframes, bool shift,
                              const LaunchPlan& p) {
-    return launch_split(a, p, kDiskBatchTiles ? kMaxGridY : wave_block_max_ny(p.tiles_x),
-                        [&](const RenderArgs& la, uint32_t ny, hipEvent_t start, hipEvent_t stop) {
-        const dim3 grid = kDiskBatchTiles ? dim3(p.tiles_x, ny, nframes)
-                                          : dim3(wave_block_count(la.launch_tiles), 1, nframes);
-        const dim3 block(kDiskBatchTiles ? kBlock : 64);
+    return launch_split(a, p, wave_block_max_ny(p.tiles_x),
+                        [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+        const dim3 grid(wave_block_count(la.launch_tiles), 1, nframes), block(64);
         if (shift)
             hipExtLaunchKernelGGL(geo_render_disk_batch_kernel<KIND, true>, grid, block, 0, p.s, start, stop, 0, la,
                                   db);
@@ -784,7 +772,6 @@ static int fill_frames(const RenderCall& rc, RenderWork& w) {
 static void fill_args(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     RenderArgs& a = w.a;
     a.out_frame_px = rc.out_frame_stride / 4u;
-    a.persist_blocks = (uint32_t)c->num_cus * 8u;  // 8 workgroups of 4 waves per CU: every wave slot
 #if defined(GEO_WAVE_LOG)
     a.wave_log = c->wave_log;
 #endif
@@ -822,8 +809,6 @@ static void fill_args(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     a.sky_wf = (float)c->sky_w;
     a.sky_hf = (float)c->sky_h;
     a.sky_total_bytes = c->sky_total_bytes;
-    a.sky_pairs_off = c->sky_pairs_off;
-    a.sky_pairs_pitch = (c->sky_w + 2u) * 8u;
     a.tile_order = nullptr;
     a.tile_cost = nullptr;
     a.cost_overhead = w.adaptive ? kCostOverheadAdaptive : kCostOverheadDirect;

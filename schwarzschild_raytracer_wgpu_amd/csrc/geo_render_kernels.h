@@ -108,7 +108,6 @@ struct RenderArgs {
     uint32_t width, height, row0, nrows;
     uint32_t tile_y0;  // first tile row of this launch (launch_tiles)
     uint32_t tiles_x, launch_tiles;  // the frame's tiles per row; the tiles of this launch (wave_blocks)
-    uint32_t persist_blocks;         // kFanPersist: workgroups of the fan draw's grid
     // dispatch order (geo_ctx): workgroup i draws tile
     // (order[i] & 0xFFFF, order[i] >> 16); null = row-major
     const uint32_t* tile_order;
@@ -131,7 +130,6 @@ struct RenderArgs {
     float mip_w256[geo::kSkyMipLevels], mip_h256[geo::kSkyMipLevels];
     float sky_wf, sky_hf;
     uint32_t sky_total_bytes;
-    uint32_t sky_pairs_off, sky_pairs_pitch;  // kSkyPairs: level 0's row pairs (PairSkyQuad)
     const float* fan;
     uint32_t n_fan;
     uint32_t* out_rgba;
@@ -193,40 +191,14 @@ struct PaddedSkyQuad {
     }
 };
 
-// A/B variant (GEO_SKY_PAIRS=1): level 0 also stored as row pairs
-// (geo::pair_sky_rows), so a bilinear quad is 16 contiguous bytes, one
-// buffer_load_dwordx4 and one 128-B line, where the row-major quad spans two
-// rows, two lines.  Measured against PaddedSkyQuad: the fan draw -0.5 to
-// -1 % (one box read the 1080p draw -8 %), config 3 +0.2 to +0.8 %, the ring
-// overhead up by half a point (profiles/r06zk_sky_pairs_ab.txt,
-// profiles/r06zl_sky_pairs_ab.txt), for a second copy of level 0 in device
-// memory: not kept.
-#if defined(GEO_SKY_PAIRS)
-constexpr bool kSkyPairs = GEO_SKY_PAIRS != 0;
-#else
-constexpr bool kSkyPairs = false;
-#endif
-struct PairSkyQuad {
-    __amdgpu_buffer_rsrc_t rsrc;
-    uint32_t base, pitch_b;  // the pairs' byte offset in the sky buffer; bytes per pair row, (sky_w + 2) * 8
-    __device__ __forceinline__ void operator()(int ix0, int iy0, uint32_t (&t)[4]) const {
-        const uint32_t off = base + __umul24((uint32_t)(iy0 + 1), pitch_b) + ((uint32_t)(ix0 + 1) << 3);
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        t[0] = v[0];  // (x, y)
-        t[2] = v[1];  // (x, y + 1)
-        t[1] = v[2];  // (x + 1, y)
-        t[3] = v[3];  // (x + 1, y + 1)
-    }
-};
-__device__ __forceinline__ auto level0_quad(const RenderArgs& a) {
-    if constexpr (kSkyPairs)
-        return PairSkyQuad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.sky), 0, (int)a.sky_total_bytes,
-                                                             kBufferRsrcWord3),
-                           a.sky_pairs_off, a.sky_pairs_pitch};
-    else
-        return PaddedSkyQuad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.sky), 0, (int)a.sky_bytes,
-                                                               kBufferRsrcWord3),
-                             a.sky_pitch_b};
+// Tried: level 0 also stored as row pairs (geo::pair_sky_rows), a quad in one
+// 16-byte load.  The fan draw -0.5 to -1 %, config 3 +0.2 to +0.8 %, the ring
+// overhead up by half a point, for a second copy of level 0: not kept
+// (profiles/r06zk_sky_pairs_ab.txt, profiles/r06zl_sky_pairs_ab.txt).
+__device__ __forceinline__ PaddedSkyQuad level0_quad(const RenderArgs& a) {
+    return PaddedSkyQuad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(a.sky), 0, (int)a.sky_bytes,
+                                                           kBufferRsrcWord3),
+                         a.sky_pitch_b};
 }
 
 // The texel quad of one mip level of the padded chain (geo_ctx::sky): like
@@ -334,38 +306,20 @@ constexpr uint32_t kBandDwords = (uint32_t)(sizeof(geo::BandConsts) / 4u);
 // as its tile's others, and a 4-wave workgroup keeps its finished waves'
 // slots from the next workgroup until it ends (config 3 +8.4 -> +7.4 %,
 // config 2 +15.0 -> +13.1 % over the plain frame, profiles/r06e_ring_wave_blocks_ab.txt).
-constexpr bool kRingWaveBlocks = true;
 // The same for a plain one-frame direct-mode render (tiles differ ~30x in
 // cost, and its waves' lifetimes within a tile differ too): config 3
 // -0.7 %, config 2 -1 % per frame; the adaptive mode measured +0.8 % and
 // keeps 4-wave workgroups (profiles/r06h_all_wave_blocks_ab.txt)
-constexpr bool kDirectWaveBlocks = true;
-// The four waves of a tile on one XCD (its L2 holds the tile's sky lines):
-// against four consecutive workgroups (on four XCDs), config 3 -0.6 to
-// -0.8 %, config 2 -0.8 % (profiles/r06k_wave_block_layout_ab.txt)
-#if defined(GEO_WB_XCD)
-constexpr bool kWaveBlocksXcd = GEO_WB_XCD != 0;
-#else
-constexpr bool kWaveBlocksXcd = true;
-#endif
-#if defined(GEO_ADAPTIVE_WAVE_BLOCKS)  // A/B variant
-constexpr bool kAdaptiveWaveBlocks = true;
-#else
-constexpr bool kAdaptiveWaveBlocks = false;
-#endif
 __host__ __device__ constexpr bool wave_blocks(int mode, bool mips, uint32_t nf, bool ring) {
-    return (ring && kRingWaveBlocks && nf == 1) ||
-           (!mips && nf == 1 &&
-            ((kDirectWaveBlocks && mode == GEO_MODE_DIRECT) || (kAdaptiveWaveBlocks && mode == GEO_MODE_ADAPTIVE)));
+    return nf == 1 && (ring || (!mips && mode == GEO_MODE_DIRECT));
 }
-#if defined(GEO_FAN_PERSIST)  // A/B variant: the fan-mode draw on a persistent grid
-constexpr bool kFanPersist = true;
-#else
-constexpr bool kFanPersist = false;
-#endif
-// WB's 1-D grid for a launch of n tiles (n <= kMaxWaveBlockTiles: at most 2^31 workgroups)
+// WB's 1-D grid for a launch of n tiles (n <= kMaxWaveBlockTiles: at most 2^31
+// workgroups): whole groups of 8 tiles, the four waves of a tile 8 workgroups
+// apart and so on one XCD (its L2 holds the tile's sky lines).  Against four
+// consecutive workgroups (on four XCDs), config 3 -0.6 to -0.8 %, config 2
+// -0.8 % (profiles/r06k_wave_block_layout_ab.txt)
 constexpr uint32_t kMaxWaveBlockTiles = 1u << 26;
-inline uint32_t wave_block_count(uint32_t n) { return kWaveBlocksXcd ? (n + 7u) / 8u * 32u : 4u * n; }
+inline uint32_t wave_block_count(uint32_t n) { return (n + 7u) / 8u * 32u; }
 static_assert(sizeof(geo::BandConsts) % 8u == 0 && kBandDwords / 2u <= 64u, "one 8-byte word per thread");
 
 // GEO_FLAG_MIPS epilogue: the pixel's UV and its quad footprint rho2 are
@@ -418,11 +372,7 @@ __device__ __forceinline__ const geo::PixelConsts& frame_consts(const RenderArgs
 // Four pixels per lane (a 32 x 32 tile, 47 VGPRs) measured the same as two
 // (4K draw 0.0373 vs 0.0370 ms, 3 x 3 interleaved, profiles/r04g_fan_lr_ab.txt):
 // the draw's waves are not short of independent work.
-#if defined(GEO_FAN_LANE_ROWS)  // A/B variant
-constexpr uint32_t kFanLaneRows = GEO_FAN_LANE_ROWS;
-#else
 constexpr uint32_t kFanLaneRows = 2;
-#endif
 __host__ __device__ constexpr uint32_t lane_rows(int mode, bool mips) {
     return mode == GEO_MODE_FAN && !mips ? kFanLaneRows : 1u;
 }
@@ -450,12 +400,6 @@ __device__ __forceinline__ void fan_tile(const RenderArgs& a, const FrameK& f, s
         py[k] = p0;
         py[k + 1] = p0 + kWaveRows;
     }
-#if defined(GEO_FAN_PROBE) && (GEO_FAN_PROBE & 4)  // diagnostic: the stores alone
-#pragma unroll
-    for (uint32_t k = 0; k < LR; ++k)
-        if (px < a.width && ly[k] < a.nrows && py[k] < a.height) a.out_rgba[obase + (size_t)ly[k] * a.width + px] = py[k];
-    return;
-#endif
     float c2x[LR], c2y[LR], st[LR], ct[LR], rct[LR], lam[LR];
 #pragma unroll
     for (uint32_t k = 0; k < LR; ++k) {
@@ -470,13 +414,7 @@ __device__ __forceinline__ void fan_tile(const RenderArgs& a, const FrameK& f, s
 #pragma unroll
     for (uint32_t k = 0; k < LR; ++k) fp[k] = geo::fan_pos(a.n_fan, st[k]);
 #pragma unroll
-    for (uint32_t k = 0; k < LR; ++k) {
-#if defined(GEO_FAN_PROBE) && (GEO_FAN_PROBE & 2)  // diagnostic: no fan loads
-        lam[k] = st[k] + fp[k].w;
-#else
-        lam[k] = geo::fan_at(a.fan, fp[k]);
-#endif
-    }
+    for (uint32_t k = 0; k < LR; ++k) lam[k] = geo::fan_at(a.fan, fp[k]);
     bool in[LR], bh[LR];
     bool all_bh = true;
 #pragma unroll
@@ -500,16 +438,8 @@ __device__ __forceinline__ void fan_tile(const RenderArgs& a, const FrameK& f, s
             const auto quad = level0_quad(a);
             uint32_t smp[LR];
 #pragma unroll
-            for (uint32_t k = 0; k < LR; ++k) {
-#if defined(GEO_FAN_PROBE) && (GEO_FAN_PROBE & 1)  // diagnostic: no texel loads
-                smp[k] = __float_as_uint(U[k]) ^ __float_as_uint(V[k]);
-                (void)quad;
-#elif defined(GEO_FAN_PROBE) && (GEO_FAN_PROBE & 8)  // diagnostic: every lane samples near one texel
-                smp[k] = geo::sample_sky_quad_f(quad, a.sky_w256, a.sky_h256, 0.5f + U[k] * 1e-6f, 0.5f);
-#else
+            for (uint32_t k = 0; k < LR; ++k)
                 smp[k] = geo::sample_sky_quad_f(quad, a.sky_w256, a.sky_h256, U[k], V[k]);
-#endif
-            }
 #pragma unroll
             for (uint32_t k = 0; k < LR; ++k)
                 rgba[k] = bh[k] ? geo::kBlackRGBA : geo::over_clear(smp[k], a.sky_opaque != 0);
@@ -542,17 +472,17 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
     const size_t obase = NF > 1 ? (size_t)z * a.out_frame_px : 0;
     // WB (wave_blocks): one wave per workgroup, on a 1-D grid: workgroup L
     // draws wave w of the tile at dispatch position p (p indexes the order,
-    // or the launch's tiles row-major).  kWaveBlocksXcd: the hardware deals
-    // workgroups to the 8 XCDs round-robin (L mod 8), so the four waves of a
-    // tile are put 8 apart (p = 8 (L / 32) + L mod 8, w = (L / 8) mod 4) and
-    // share their XCD's L2 for the tile's sky lines; the grid is padded to
-    // whole groups of 8 tiles.  Otherwise p = L / 4, w = L mod 4.
+    // or the launch's tiles row-major).  The hardware deals workgroups to
+    // the 8 XCDs round-robin (L mod 8), so the four waves of a tile are put 8
+    // apart (p = 8 (L / 32) + L mod 8, w = (L / 8) mod 4) and share their
+    // XCD's L2 for the tile's sky lines; the grid is padded to whole groups
+    // of 8 tiles (wave_block_count).
     constexpr bool WB = wave_blocks(MODE, MIPS, NF, RING);
     uint32_t pos, wave;
     if constexpr (WB) {
         const uint32_t L = blockIdx.x;
-        pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
-        wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+        pos = ((L >> 5) << 3) + (L & 7u);
+        wave = (L >> 3) & 3u;
         if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
     } else {
         pos = blockIdx.y * gridDim.x + blockIdx.x;
@@ -594,14 +524,7 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
     (void)cost_scale;
     const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
     if constexpr (LR > 1) {
-        if constexpr (kFanPersist) {
-            // a persistent grid (its tiles all cost the same): workgroup b
-            // draws tiles b, b + G, ... of the launch
-            for (uint32_t t = blockIdx.x; t < a.launch_tiles; t += gridDim.x)
-                fan_tile<LR>(a, f, obase, make_uint2(t % a.tiles_x, a.tile_y0 + t / a.tiles_x), wave, lane);
-        } else {
-            fan_tile<LR>(a, f, obase, tile, wave, lane);
-        }
+        fan_tile<LR>(a, f, obase, tile, wave, lane);
     } else if constexpr (!MIPS) {
         if (in_frame) {
             float c2x, c2y, c2z;
@@ -622,9 +545,6 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
                 else
                     kx = bkl.kx;
                 const bool band = geo::in_band(kx, ct);
-#if defined(GEO_RING_PRIO)  // A/B variant: a wave with band lanes issues first
-                if (geo::ballot_(band) != 0) __builtin_amdgcn_s_setprio(GEO_RING_PRIO);
-#endif
                 float lam = 0.0f;
                 bool bh = false;
                 if (!band) {
@@ -770,8 +690,8 @@ __global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a,
                                                              const DiskArgs d) {
     const FrameK& f = fb.f[0];
     const uint32_t L = blockIdx.x;
-    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
-    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
     if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
     const uint32_t tiles_x = a.tiles_x;
     uint2 tile;
@@ -839,8 +759,8 @@ __global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderA
                                                                    const DiskArgs d, const DiskShiftArgs sh) {
     const FrameK& f = fb.f[0];
     const uint32_t L = blockIdx.x;
-    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
-    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
     if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
     const uint32_t tiles_x = a.tiles_x;
     uint2 tile;
@@ -929,32 +849,19 @@ struct DiskBatchArgs {
 
 // Launch geometry: the one-frame disk render's, one wave per workgroup on the
 // 1-D wave-block grid, with the frame in grid.z.  The plain batch's 32 x 8-pixel
-// workgroups of four waves on a 2-D grid (the A/B variant GEO_DISK_BATCH_TILES)
-// were measured against it.
-#if defined(GEO_DISK_BATCH_TILES)  // A/B variant
-constexpr bool kDiskBatchTiles = true;
-#else
-constexpr bool kDiskBatchTiles = false;
-#endif
+// workgroups of four waves on a 2-D grid were measured against it.
 
 // SHIFT: the shaded batch (geo_set_disk_shift).  One template: no kernel that
 // existed before shares a body with it.
 template <int KIND, bool SHIFT>
-__global__ __launch_bounds__(kDiskBatchTiles ? kBlock : 64) void geo_render_disk_batch_kernel(const RenderArgs a,
-                                                                                            const DiskBatchArgs db) {
+__global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderArgs a, const DiskBatchArgs db) {
     const uint32_t z = blockIdx.z;
     const DiskFrameK& f = db.f[z];
     const size_t obase = (size_t)z * a.out_frame_px;
-    uint32_t pos, wave;
-    if constexpr (kDiskBatchTiles) {
-        pos = blockIdx.y * a.tiles_x + blockIdx.x;
-        wave = __builtin_amdgcn_readfirstlane(threadIdx.x) >> 6;
-    } else {
-        const uint32_t L = blockIdx.x;
-        pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
-        wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
-        if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    }
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
     const uint32_t tiles_x = a.tiles_x;
     uint2 tile;
     if (a.tile_order) {
@@ -1095,8 +1002,8 @@ __global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, c
                                                            const SsArgs<VAR> x) {
     const FrameK& f = fb.f[0];
     const uint32_t L = blockIdx.x;
-    const uint32_t pos = kWaveBlocksXcd ? ((L >> 5) << 3) + (L & 7u) : L >> 2;
-    const uint32_t wave = kWaveBlocksXcd ? (L >> 3) & 3u : L & 3u;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
     if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
     const uint32_t tiles_x = a.tiles_x;
     uint2 tile;

@@ -79,8 +79,8 @@ extern "C" int host_sample_padded(const uint32_t* sky, uint32_t sw, uint32_t sh,
     uint32_t* pad = new uint32_t[((size_t)sw + 2) * ((size_t)sh + 2)];
     geo::pad_sky(reinterpret_cast<const uint8_t*>(sky), sw, sh, pad);
     const uint32_t pitch = sw + 2u;
-    // the row pairs the device reads (geo::pair_sky_rows, PairSkyQuad): the
-    // quad at padded (x, y) is the 4 texels from 2 (y pitch + x)
+    // the row pairs (geo::pair_sky_rows; a host-side layout, no kernel reads
+    // it): the quad at padded (x, y) is the 4 texels from 2 (y pitch + x)
     uint32_t* pairs = new uint32_t[2 * ((size_t)sw + 2) * ((size_t)sh + 1)];
     geo::pair_sky_rows(pad, sw, sh, pairs);
     auto paired = [pairs, pitch](int ix0, int iy0, uint32_t (&t)[4]) {
