@@ -57,11 +57,13 @@ extern "C" {
                                    announced by GEO_HAS_DISK_SHIFT: geo_disk_shift,
                                    geo_set_disk_shift, geo_disk_shift_next_render;
                                    announced by GEO_HAS_DISK_BATCH: geo_render_disk_batch;
-                                   announced by GEO_HAS_SS4: GEO_FLAG_SS4) */
+                                   announced by GEO_HAS_SS4: GEO_FLAG_SS4;
+                                   announced by GEO_HAS_SS4_BATCH: geo_render_ss_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
 #define GEO_HAS_SS4 1
+#define GEO_HAS_SS4_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -178,7 +180,10 @@ typedef enum geo_status {
                                    the sample frame's, ceil(2 width / 32) x ceil(2 nrows / 8).
                                    No buffer of samples is kept: a wave's 16 x 4 samples are
                                    8 x 2 output pixels, resolved across its lanes
-                                   (DESIGN.md §3). */
+                                   (DESIGN.md §3).  Up to GEO_MAX_BATCH_FRAMES supersampled
+                                   frames in one launch go through geo_render_ss_batch
+                                   (GEO_HAS_SS4_BATCH), the only batched call that takes the
+                                   flag. */
 #define GEO_DISK_MAX_CROSSINGS 3
 #define GEO_DISK_G_MAX 16.0f    /* the largest frequency ratio a shaded hit reports
                                    (geo_set_disk_shift; csrc/geo_disk.h) */
@@ -440,6 +445,41 @@ int geo_render_disk_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene
                           uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                           uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                           unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for GEO_FLAG_SS4 scenes (GEO_HAS_SS4_BATCH): nframes
+ * (1 .. GEO_MAX_BATCH_FRAMES) 2 x 2 supersampled frames in ONE launch, scenes[f]
+ * for frames[f]: the plain frame, the GEO_FLAG_DISK frame and, with
+ * geo_set_disk_shift, the shaded disk frame.  width, height, rows and bands are
+ * in output pixels, as for the one-frame supersampled render; frame f's packed
+ * bands go to out_rgba8 + f*out_frame_stride bytes (out_frame_stride a multiple
+ * of 4, at least nbands*band_rows*width*4).  Frame f's bytes are those of
+ * geo_render_band_set with frames[f] and scenes[f] (the same flags), bit for
+ * bit, and so, by GEO_FLAG_SS4's definition, the box resolve of the one-sample
+ * render at twice the size.
+ * Every scene carries GEO_FLAG_SS4 and GEO_MODE_DIRECT, with GEO_FLAG_DISK and
+ * GEO_FLAG_DEFER_STEPS at most; a scene without GEO_FLAG_SS4 is GEO_EINVAL (the
+ * other batched calls draw those).  The scenes may differ in r_obs only and
+ * share the integration kind (geo_render_band_set_batch's rules), else
+ * GEO_EINVAL.  With GEO_FLAG_DISK, geo_render_disk_batch's rules hold for every
+ * frame's scene.  GEO_ESTATE when no sky, or no disk for a disk scene, is set.
+ * Colour only: a buffer armed by geo_disk_hits_next_render or
+ * geo_disk_shift_next_render is consumed and the call returns GEO_EINVAL.  The
+ * one-frame supersampled render's size limits apply: width and height at most
+ * 2^19 (and twice a band layout's rows within what the call takes as rows).  A
+ * refused call launches nothing and writes nothing; ctx, frames, scenes or
+ * out_rgba8 NULL and nframes out of range are refused before any device work.
+ * The steps of every sample of every frame go to steps_total or, with
+ * GEO_FLAG_DEFER_STEPS, to the context's accumulator.  geo_time_next_render
+ * works as for the other batches.  The tile grid, for the learned order and
+ * for geo_set_tile_order alike, is the sample frame's, ceil(2 width / 32) x
+ * ceil(2 nrows / 8); frame 0 records the tile costs, the learned order is per
+ * tile and is the one-frame supersampled render's own for the same grid.
+ * geo_render_band_set_frames / _batch and geo_render_disk_batch keep refusing
+ * the flag.  One scene for every frame: pass copies.  Asynchronous on `stream`. */
+int geo_render_ss_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                        uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                        uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                        unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

@@ -37,6 +37,7 @@ GEO_DISK_MAX_CROSSINGS = 3
 GEO_RING_X = 5e-3
 GEO_MAX_BATCH_FRAMES = 8
 GEO_HAS_DISK_BATCH = 1  # geo_render_disk_batch
+GEO_HAS_SS4_BATCH = 1  # geo_render_ss_batch
 
 GEO_RAYS_NEAR = 1
 GEO_RAYS_FAR = 2
@@ -141,6 +142,11 @@ SIGNATURES = {
          ctypes.c_size_t, _vp, _vp],
     ),
     "geo_render_disk_batch": (
+        _int,
+        [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
+         ctypes.c_size_t, _vp, _vp],
+    ),
+    "geo_render_ss_batch": (
         _int,
         [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
          ctypes.c_size_t, _vp, _vp],

@@ -643,6 +643,9 @@ struct RenderCall {
     // geo_render_disk_batch (GEO_FLAG_DISK scenes, any nframes, through the
     // batched disk kernel); the other entry points draw a disk frame alone
     bool disk_batch = false;
+    // geo_render_ss_batch (GEO_FLAG_SS4 scenes, any nframes, through the
+    // batched SS kernels); the other entry points draw an SS frame alone
+    bool ss_batch = false;
     uint32_t width, height, row0, nrows, band_rows, band_stride;
     uint8_t* out_rgba8;
     uint8_t* out_mask = nullptr;  // (a batch draws colour only)
@@ -679,17 +682,22 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
         return GEO_EINVAL;
     // GEO_FLAG_SS4 (every rule here, where the bit was refused as an unknown
     // one before: a call that breaks an older rule too keeps its status): the
-    // one-frame entry points (the ones that draw a disk frame alone), direct
-    // mode, the level-0 sampler, colour only (an armed hit or g buffer,
-    // consumed by render_impl, refuses the call), DISK and DEFER_STEPS at
-    // most, and a sample frame of twice the size that the entry points take
+    // one-frame entry points (the ones that draw a disk frame alone) and
+    // geo_render_ss_batch, direct mode, the level-0 sampler, colour only (an
+    // armed hit or g buffer, consumed by render_impl, refuses the call), DISK
+    // and DEFER_STEPS at most, and a sample frame of twice the size that the
+    // entry points take
     w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
-    if (w.ss && (!rc.allow_disk || rc.disk_batch || rc.nframes != 1 || scene->mode != GEO_MODE_DIRECT ||
+    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && rc.nframes != 1) ||
+                 scene->mode != GEO_MODE_DIRECT ||
                  (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
                  rc.out_uv || rc.out_steps || w.out_hits || w.out_g || rc.width > (1u << 19) ||
                  rc.height > (1u << 19)))
         return GEO_EINVAL;
-    // GEO_FLAG_DISK: the one-frame entry points and geo_render_disk_batch, direct mode, DEFER_STEPS at most
+    // geo_render_ss_batch draws SS4 scenes only (the other batched calls draw the rest)
+    if (rc.ss_batch && !w.ss) return GEO_EINVAL;
+    // GEO_FLAG_DISK: the one-frame entry points, geo_render_disk_batch and (with SS4) geo_render_ss_batch, direct
+    // mode, DEFER_STEPS at most
     w.disk = (scene->flags & GEO_FLAG_DISK) != 0;
     if (w.disk && (!rc.allow_disk || scene->mode != GEO_MODE_DIRECT ||
                    (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0))
@@ -986,10 +994,10 @@ static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderW
     });
 }
 
-// Stage 5, geo_render_disk_batch: every frame's constants by the one-frame
-// launch's own functions.
-static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    DiskBatchArgs db;
+// A batch's DiskBatchArgs: every frame's constants by the one-frame launch's
+// own functions (geo_render_disk_batch, and geo_render_ss_batch's disk frames,
+// whose w.fk holds the sample frame's camera).
+static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderWork& w, DiskBatchArgs& db) {
     std::memset(&db, 0, sizeof(db));
     for (uint32_t i = 0; i < rc.nframes; ++i) {
         const geo_scene& si = rc.scene_per_frame ? rc.scene[i] : *rc.scene;
@@ -1027,14 +1035,60 @@ static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const Rend
         }
     }
     fill_disk_tex(c, db);
+    return GEO_OK;
+}
+
+// Stage 5, geo_render_disk_batch.
+static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    DiskBatchArgs db;
+    if (const int st = fill_disk_batch(c, rc, w, db)) return st;
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
         return launch_disk_batch<decltype(kind)::value>(w.a, db, rc.nframes, c->shift_set, w.p);
     });
 }
 
+// Stage 5, geo_render_ss_batch: launch_ss_frame's three variants with the
+// frames in grid.z (geo_render_ss_batch_kernel), on the disk batch's geometry.
+// w.fk holds each frame's camera at 2W x 2H and w.pk its scene constants
+// (fill_frames); the disk frames' constants are fill_disk_batch's.
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<kMaxBatchFrames>) + sizeof(SsBatchOut) <= 4096,
+              "kernel arguments fit 4 KiB");
+static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(SsBatchOut) <= 4096, "kernel arguments fit 4 KiB");
+static int launch_ss_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    SsBatchOut x;
+    x.out_width = rc.width;
+    FrameBatch<kMaxBatchFrames> fb;
+    DiskBatchArgs db;
+    if (w.disk) {
+        if (const int st = fill_disk_batch(c, rc, w, db)) return st;
+    } else {
+        std::memset(&fb, 0, sizeof(fb));
+        for (uint32_t i = 0; i < rc.nframes; ++i) {
+            fb.f[i] = w.fk[i];
+            fb.k[i] = w.pk[i];
+        }
+    }
+    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
+                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+            const dim3 grid(wave_block_count(la.launch_tiles), 1, rc.nframes), block(64);
+            if (!w.disk)
+                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsPlain>), grid, block, 0, w.p.s, start, stop,
+                                      0, la, fb, x);
+            else if (!c->shift_set)
+                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsDisk>), grid, block, 0, w.p.s, start, stop,
+                                      0, la, db, x);
+            else
+                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsDiskShift>), grid, block, 0, w.p.s, start,
+                                      stop, 0, la, db, x);
+        });
+    });
+}
+
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    if (w.ss) return launch_ss_frame(c, rc, w);
+    if (w.ss) return rc.ss_batch ? launch_ss_frames(c, rc, w) : launch_ss_frame(c, rc, w);
     if (w.disk) return rc.disk_batch ? launch_disk_frames(c, rc, w) : launch_disk_frame(c, rc, w);
     if (rc.scene->mode == GEO_MODE_FAN) return launch_fan(c, rc, w);
     geo::BandConsts band_k;  // (one frame; a batch derives its frames' constants on the device)
@@ -1440,6 +1494,23 @@ int geo_render_disk_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* 
     rc.scene_per_frame = true;
     rc.allow_disk = true;
     rc.disk_batch = true;
+    return render_impl(c, rc);
+}
+
+int geo_render_ss_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                        uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                        uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                        unsigned long long* steps_total, void* stream) {
+    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
+        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
+        return invalid_call(c);
+    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
+                                out_rgba8, steps_total, stream);
+    rc.nframes = nframes;
+    rc.out_frame_stride = out_frame_stride;
+    rc.scene_per_frame = true;
+    rc.allow_disk = true;
+    rc.ss_batch = true;
     return render_impl(c, rc);
 }
 

@@ -1087,6 +1087,145 @@ __global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, c
     disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
 }
 
+// ---- geo_render_ss_batch: up to kMaxBatchFrames GEO_FLAG_SS4 frames in one launch --
+// geo_render_ss_kernel with the frame in blockIdx.z, on the disk batch's
+// geometry: one wave per workgroup on the 1-D wave-block grid, grid.z frames.
+// Frame z's constants come from the batched kernels' own argument structs,
+// indexed by z (uniform: scalar loads): the plain variant reads
+// FrameBatch<kMaxBatchFrames> (f[z], k[z]), the disk variants DiskBatchArgs
+// (DiskFrameK, assembled into geo::DiskConsts and geo::DiskShift as
+// geo_render_disk_batch_kernel does).  The host fills both with the one-frame
+// SS launch's functions at the sample frame's size, so a batch frame is its
+// one-frame render bit for bit.  The output's pitch rides in SsBatchOut; frame
+// z's output starts a.out_frame_px output pixels after frame z - 1's.
+struct SsBatchOut {
+    uint32_t out_width;  // the output's pitch in pixels (RenderArgs::width is the sample frame's, twice it)
+};
+template <int VAR>
+struct SsBatchFrames {
+    using type = DiskBatchArgs;
+};
+template <>
+struct SsBatchFrames<kSsPlain> {
+    using type = FrameBatch<kMaxBatchFrames>;
+};
+
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) void geo_render_ss_batch_kernel(const RenderArgs a,
+                                                                 const typename SsBatchFrames<VAR>::type fb,
+                                                                 const SsBatchOut x) {
+    const uint32_t z = blockIdx.z;
+    const auto& f = fb.f[z];
+    const size_t obase = (size_t)z * a.out_frame_px;
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    // the only early exit, and a wave-uniform one: ss_resolve below needs every lane
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // the sample grid, the band mapping on output rows and the quads' parity:
+    // geo_render_ss_kernel's, which see
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // the sample's colour, kept in a register
+    if (in_frame) {
+        if constexpr (VAR == kSsPlain) {
+            float c2x, c2y, c2z;
+            geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                                   &c2x, &c2y, &c2z);
+            const float st = geo::central_sin(c2z);
+            const float ct = geo::central_rho(c2x, c2y);
+            const float rct = geo::rcpf_(ct);
+            const float lam = pixel_lambda<GEO_MODE_DIRECT, KIND>(a, fb.k[z], st, ct, rct, &steps);
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+            colour = bh ? geo::kBlackRGBA
+                        : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        } else {
+            float c2x, c2y, c2z, g_obs = 0.0f;
+            if constexpr (VAR == kSsDiskShift)
+                geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
+            else
+                geo::pixel_central_dir(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z);
+            const float st = geo::central_sin(c2z);
+            const float ct = geo::central_rho(c2x, c2y);
+            const float rct = geo::rcpf_(ct);
+            // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
+            geo::DiskConsts dk;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                dk.N[i] = f.N[i];
+                dk.ex[i] = f.ex[i];
+                dk.ey[i] = f.ey[i];
+            }
+            dk.r_in = fb.r_in;
+            dk.r_out = fb.r_out;
+            dk.inv_dr = fb.inv_dr;
+            dk.u_lo = f.u_lo;
+            dk.u_hi = f.u_hi;
+            dk.inv_step = fb.inv_step;
+            const geo::PixelConsts& k = f.k;
+            geo::DiskRay dr;
+            geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+            float Uk[geo::kDiskMaxCrossings];
+            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            const float lam = geo::kPi2 - ang;
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+            const uint32_t base = bh ? geo::kBlackRGBA
+                                     : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+            const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(fb.tex), 0,
+                                                                        (int)fb.tex_bytes, kBufferRsrcWord3),
+                                      fb.tex_pitch_b};
+            const auto dsample = [&](float Ud, float Vd) {
+                return geo::sample_sky_quad_f(dquad, fb.tex_w256, fb.tex_h256, Ud, Vd);
+            };
+            if constexpr (VAR == kSsDiskShift) {
+                geo::DiskShift sk;
+                sk.sb = f.sb;
+                sk.ih = f.ih;
+                sk.gain = fb.gain;
+                sk.exponent = fb.exponent;
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
+                colour = geo::disk_shade_shift(dk, k, dr, sk, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
+            } else {
+                colour = geo::disk_shade(dk, k, dr, Uk, steps, ang, base, dsample, nullptr);
+            }
+        }
+    }
+    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
+    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
+    // of the frame resolves four zeros and is not stored.
+    const uint32_t resolved = ss_resolve(colour);
+    if (in_frame && (lane & 0x11u) == 0u)
+        a.out_rgba[obase + (size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1506,6 +1645,15 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_ss_kernel<geo::kCurvedOut, kSsDiskShift>;
     (void)geo_render_ss_kernel<geo::kCurvedIn, kSsDiskShift>;
     (void)geo_render_ss_kernel<geo::kFlat, kSsDiskShift>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsPlain>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsPlain>;
+    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsPlain>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsDisk>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsDisk>;
+    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsDisk>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsDiskShift>;
+    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsDiskShift>;
+    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsDiskShift>;
 }
 
 }  // namespace

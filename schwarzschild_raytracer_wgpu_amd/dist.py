@@ -336,11 +336,12 @@ class ShardedFrame:
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
         """The frames of batch buffer b (slots first .. first + len(frames) - 1)
-        in one launch (geo_render_band_set_batch, or geo_render_disk_batch
-        for GEO_FLAG_DISK scenes), on `stream` (a handle;
+        in one launch (geo_render_band_set_batch, geo_render_ss_batch for
+        GEO_FLAG_SS4 scenes, or geo_render_disk_batch for GEO_FLAG_DISK
+        scenes without it), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
-        from ._lib import GEO_FLAG_DISK, GeoFrame, GeoScene, check
+        from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4, GeoFrame, GeoScene, check
 
         band_h, row0, cycle, nb = self._band
         sh = self._sh[b % self.S] if stream is None else stream
@@ -356,9 +357,15 @@ class ShardedFrame:
             scenes = [self.scene if scene is None else scene] * n
         self._frame_arr = (GeoFrame * n)(*frames)
         self._scene_arr = (GeoScene * n)(*scenes)
-        # thin-disk scenes have a batched entry point of their own
-        # (_batch_key keeps a launch's flags equal)
-        name = "geo_render_disk_batch" if scenes[0].flags & GEO_FLAG_DISK else "geo_render_band_set_batch"
+        # supersampled scenes (with a disk or without) and thin-disk scenes
+        # have batched entry points of their own (_batch_key keeps a launch's
+        # flags equal)
+        if scenes[0].flags & GEO_FLAG_SS4:
+            name = "geo_render_ss_batch"
+        elif scenes[0].flags & GEO_FLAG_DISK:
+            name = "geo_render_disk_batch"
+        else:
+            name = "geo_render_band_set_batch"
         st = getattr(self.lib, name)(
             self._ctx_h, self._frame_arr, self._scene_arr, n, self.width, self.height, band_h, row0, cycle, nb,
             self._lv[b][first], self.slice, None, sh)

@@ -19,6 +19,23 @@ margin the SS frame is held to is 1 + 2 x that spread.  Writes one JSON object
 with every session (profiles/ss_bench_cfg3.json by default) and prints it.
 
   python tools/bench_ss.py [--n 30] [--rounds 5] [--sessions 2] [--out profiles/ss_bench_cfg3.json]
+
+  python tools/bench_ss.py --batch 8 [--n 30] [--rounds 5] [--sessions 1] [--out profiles/ss_batch_bench_cfg3.json]
+
+--batch K measures the batched SS launch (geo_render_ss_batch) where it is
+used: a peer's share of the 1920 x 1080 supersampled frame at N = 8 (8-row
+bands, BandLayout rank 1 of 8; the sample frame is the 4K frame).  One launch of
+K frames alternates with K one-frame geo_render_band_set launches of the same
+frames back to back (the kernels this build has unchanged from the commit
+before the batch), each on its own context, for the plain, the disk and the
+shifted disk frame.  Every alternation takes --n samples of each side and keeps
+their medians; --rounds alternations are timed by a pair of stream events
+around the launches (what a pipeline waits for: dispatch gaps included) and
+--rounds more by geo_time_next_render pairs on the kernel dispatches alone (the
+K one-frame times added up).  Per kind and timing: the median of the
+alternation medians per frame, the ratio batch over one-frame launches, the
+one-frame side's spread ((max - min) / median of its alternation medians) and
+the margin 1 + 2 x that spread the batch is held to.
 """
 from __future__ import annotations
 
@@ -86,14 +103,108 @@ def session(args, cfg, frame, scenes, sky, tex):
     return res
 
 
+def batch_session(args, cfg, frame, scenes, sky, tex):
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.dist import BandLayout
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent, hipEventDefault
+
+    K = args.batch
+    W, H = cfg.width // 2, cfg.height // 2
+    L = BandLayout(H, 8, 8, 1)  # a peer's share at N = 8
+    band = (L.band_height(), L.row0(), L.cycle_rows, L.nbands())
+    packed = L.packed_rows() * W * 4
+    dev = torch.device("cuda:0")
+    out = torch.empty(K * packed, dtype=torch.uint8, device=dev)
+    sh = torch.cuda.current_stream().cuda_stream
+    lib = _lib.lib
+
+    def make_ctx(kind):
+        c = g.Context(0)
+        c.set_sky(sky)
+        if kind != "plain":
+            c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+        if kind == "shift":
+            c.set_disk_shift(1, 4, 1.0)
+        return c
+
+    res = {"layout": {"world": 8, "rank": 1, "band_rows": band[0], "row0": band[1], "row_stride": band[2],
+                      "nbands": band[3], "rows": L.rows_mine()}}
+    for kind in ("plain", "disk", "shift"):
+        scene = scenes[kind][1]
+        frames = (_lib.GeoFrame * K)(*([frame] * K))
+        sarr = (_lib.GeoScene * K)(*([scene] * K))
+
+        def run_batch(c, pairs=None):
+            if pairs is not None:
+                c.time_next_render(*pairs[0])
+            _lib.check("geo_render_ss_batch", lib.geo_render_ss_batch(
+                c._h, frames, sarr, K, W, H, *band, out.data_ptr(), packed, None, sh))
+
+        def run_singles(c, pairs=None):
+            for k in range(K):
+                if pairs is not None:
+                    c.time_next_render(*pairs[k])
+                _lib.check("geo_render_band_set", lib.geo_render_band_set(
+                    c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None,
+                    None, None, None, sh))
+
+        # (each side on its own context: the learned dispatch order is kept per context)
+        sides = [("batch", make_ctx(kind), run_batch, 1), ("single", make_ctx(kind), run_singles, K)]
+        for _ in range(args.warmup):
+            for _, c, run, _ in sides:
+                run(c)
+        torch.cuda.synchronize()
+        res[kind] = {}
+        for how in ("stream_events", "dispatch_events"):
+            med = {name: [] for name, *_ in sides}
+            for _ in range(args.rounds):
+                ev = {name: [] for name, *_ in sides}
+                for _ in range(args.n):
+                    for name, c, run, m in sides:
+                        if how == "stream_events":
+                            a, b = HipEvent(hipEventDefault), HipEvent(hipEventDefault)
+                            a.record(sh)
+                            run(c)
+                            b.record(sh)
+                            ev[name].append([(a, b)])
+                        else:
+                            pairs = [(HipEvent(), HipEvent()) for _ in range(m)]
+                            run(c, pairs)
+                            ev[name].append(pairs)
+                    torch.cuda.synchronize()  # the next sample's launches queue behind nothing
+                for name, v in ev.items():
+                    med[name].append(float(np.median([sum(a.elapsed_time(b) for a, b in pairs) for pairs in v]) / K))
+            b_m, s_m = float(np.median(med["batch"])), float(np.median(med["single"]))
+            spread = (max(med["single"]) - min(med["single"])) / s_m
+            res[kind][how] = {
+                "batch_ms_per_frame_medians": med["batch"], "single_ms_per_frame_medians": med["single"],
+                "batch_ms_per_frame": b_m, "single_ms_per_frame": s_m, "batch_over_single": b_m / s_m,
+                "single_spread": spread, "batch_spread": (max(med["batch"]) - min(med["batch"])) / b_m,
+                "margin": 1.0 + 2.0 * spread, "within_margin": bool(b_m <= s_m * (1.0 + 2.0 * spread)),
+            }
+        for _, c, *_ in sides:
+            c.close()
+    return res
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=30, help="timed dispatches of each kind per alternation")
     p.add_argument("--rounds", type=int, default=5, help="alternations per session")
     p.add_argument("--sessions", type=int, default=2)
     p.add_argument("--warmup", type=int, default=40, help="untimed renders of each kind first")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "ss_bench_cfg3.json"))
+    p.add_argument("--batch", type=int, default=0, metavar="K",
+                   help="measure one launch of K SS frames against K one-frame launches (a peer's share at N = 8)")
+    p.add_argument("--out")
     args = p.parse_args()
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "ss_batch_bench_cfg3.json" if args.batch else "ss_bench_cfg3.json")
 
     import torch
 
@@ -101,6 +212,8 @@ def main():
     from schwarzschild_raytracer_wgpu_amd import _lib
     from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
 
+    if args.batch and not 1 <= args.batch <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise SystemExit(f"--batch: 1 .. {_lib.GEO_MAX_BATCH_FRAMES}")
     if not torch.cuda.is_available():
         raise SystemExit("bench_ss.py needs a HIP device")
     cfg = CONFIGS["cfg3_4k"]
@@ -117,6 +230,24 @@ def main():
     D, S = _lib.GEO_FLAG_DISK, _lib.GEO_FLAG_SS4
     scenes = {"plain": (scene(0), scene(S)), "disk": (scene(D), scene(D | S)), "shift": (scene(D), scene(D | S))}
     sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    if args.batch:
+        res = {
+            "config": "cfg3_4k", "supersampled": [cfg.width // 2, cfg.height // 2],
+            "sample_frame": [cfg.width, cfg.height], "max_steps": cfg.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs],
+            "shift": [1, 4, 1.0], "frames_per_batch": args.batch, "n": args.n, "rounds": args.rounds,
+            "warmup": args.warmup,
+            "timing": "stream_events: a pair of events on the stream around one launch of K frames, or around K "
+                      "one-frame launches back to back; dispatch_events: geo_time_next_render pairs on the kernel "
+                      "dispatches, the K one-frame times added; the two sides alternate; per alternation the median "
+                      "of n; spread = (max - min) / median of a side's alternation medians; margin = 1 + 2 x the "
+                      "one-frame side's spread",
+            "sessions": [batch_session(args, cfg, frame, scenes, sky, tex) for _ in range(args.sessions)],
+        }
+        print(json.dumps(res))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+        return
     res = {
         "config": "cfg3_4k", "one_sample": [cfg.width, cfg.height], "supersampled": [cfg.width // 2, cfg.height // 2],
         "max_steps": cfg.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs], "shift": [1, 4, 1.0],
