@@ -58,12 +58,15 @@ extern "C" {
                                    geo_set_disk_shift, geo_disk_shift_next_render;
                                    announced by GEO_HAS_DISK_BATCH: geo_render_disk_batch;
                                    announced by GEO_HAS_SS4: GEO_FLAG_SS4;
-                                   announced by GEO_HAS_SS4_BATCH: geo_render_ss_batch) */
+                                   announced by GEO_HAS_SS4_BATCH: geo_render_ss_batch;
+                                   announced by GEO_HAS_DISK_EMISSION: geo_disk_emission,
+                                   geo_set_disk_emission, geo_disk_emission_next_render) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
 #define GEO_HAS_SS4 1
 #define GEO_HAS_SS4_BATCH 1
+#define GEO_HAS_DISK_EMISSION 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -321,6 +324,62 @@ int geo_set_disk_shift(geo_ctx* ctx, const geo_disk_shift* shift);
  * by a shaded GEO_FLAG_DISK render. */
 int geo_disk_shift_next_render(geo_ctx* ctx, float* out_g);
 
+/* Blackbody emission of the disk (csrc/geo_disk.h): the disk's colour comes
+ * from a temperature instead of the texture alone.  The emitted temperature is
+ * T(r) = t_ref tau(r) with the radial profile tau below, the observed one
+ * T_obs = g T(r) with the frequency ratio g of geo_disk_shift (this struct's
+ * own spin), and q = T_obs / t_ref = g tau(r), in 0..GEO_DISK_G_MAX.  A hit is
+ * coloured by the ramp at
+ *   (n - 1) (1/t_lo - 1/T_obs) / (1/t_lo - 1/t_hi), clamped to 0..n-1
+ * (q = 0 or a NaN: entry 0), the two neighbouring entries blended per 8-bit
+ * channel with the weight w = floor(frac * 256): (a (256 - w) + b w + 128) >> 8.
+ * Each of R, G and B of the hit's disk-texture sample t and the ramp colour e
+ * becomes min(255, floor(t e m / 255 + 0.5)) with the bolometric multiplier
+ * m = min(exposure q^4, 65536), which holds the g^4 beaming; the texture's
+ * alpha is kept, and that colour is what is blended, far to near, as ever.  A
+ * white opaque texture draws the pure ramp; a patterned or translucent one
+ * modulates it. */
+#define GEO_DISK_PROFILE_POWER 0u  /* tau(r) = (r_in/r)^(3/4) */
+#define GEO_DISK_PROFILE_THIN  1u  /* zero-torque inner edge: tau(r) = f(r_in/r) / f_max,
+                                      f(x) = x^(3/4) (1 - sqrt x)^(1/4), f_max = f(36/49) = 0.487871339...;
+                                      tau = 0 at r_in, 1 at r = 49/36 r_in */
+#define GEO_DISK_RAMP_MAX 1024u
+typedef struct geo_disk_emission {
+    int32_t  spin;      /* +1 or -1, as geo_disk_shift.spin */
+    uint32_t profile;   /* GEO_DISK_PROFILE_* */
+    float    t_ref;     /* the profile's hottest emitted temperature: T(r) = t_ref tau(r) */
+    float    t_lo, t_hi;/* the ramp's ends, 0 < t_lo < t_hi: entry 0 is the colour of T_obs <= t_lo,
+                           entry n-1 of T_obs >= t_hi, the entries evenly spaced in 1/T (mired) */
+    float    exposure;  /* finite, > 0: colour multiplier m = min(exposure q^4, 65536), q = T_obs / t_ref */
+} geo_disk_emission;
+
+/* Turns the emission on for this context's GEO_FLAG_DISK renders and uploads
+ * its ramp (n RGBA8 entries, host memory; copied synchronously after this
+ * context's renders in flight, as geo_set_disk copies its texture), or turns it
+ * off with NULL (ramp and n are then ignored).  While it is set the state of
+ * geo_set_disk_shift is neither read nor changed; it takes effect again once
+ * the emission is cleared.  GEO_EINVAL for a spin other than +1 or -1, an
+ * unknown profile, a t_ref, t_lo, t_hi or exposure that is not finite and
+ * positive, t_lo >= t_hi, a NULL ramp, or n outside 2..GEO_DISK_RAMP_MAX; a
+ * refused call leaves the state as it was.  The state is kept across
+ * geo_set_disk and cleared by geo_clear_disk.  At render time the shift's rule
+ * holds: rs == 0 or r_in > 1.5 rs (GEO_EINVAL otherwise).
+ * Entry points: geo_render_rows, geo_render_bands and geo_render_band_set with
+ * all the per-pixel outputs (out_g of geo_disk_shift_next_render is written
+ * too), and GEO_FLAG_SS4 on those three, colour only.  geo_render_disk_batch,
+ * and geo_render_ss_batch for a GEO_FLAG_DISK scene, return GEO_EINVAL while an
+ * emission is set, launch nothing and write nothing: a batched disk frame
+ * would come out without its emission.  Batched emission frames are the
+ * stated follow-up. */
+int geo_set_disk_emission(geo_ctx* ctx, const geo_disk_emission* emission, const uint8_t* ramp_rgba8, uint32_t n);
+/* The next render of this context writes its hits' q = T_obs / t_ref to out_q
+ * (device, nrows*width*3 floats, laid out as the render's rows): element k of
+ * a pixel is the q of crossing k, or 0 when that crossing is not a hit.  Armed
+ * and consumed as geo_disk_hits_next_render's buffer is (an armed buffer
+ * refuses a GEO_FLAG_SS4 or a batched call); written only by an emission
+ * render. */
+int geo_disk_emission_next_render(geo_ctx* ctx, float* out_q);
+
 /* Uploads a ray fan of n >= 2 nodes (host memory, copied synchronously after
  * the last solve and draws of the buffer it goes to; geo_solve_ray_fan
  * replaces it stream-ordered):
@@ -435,8 +494,11 @@ int geo_render_band_set_batch(geo_ctx* ctx, const geo_frame* frames, const geo_s
  * every frame's scene: rs == 0, or r_obs > rs and rs < r_in; r_out < sphere_r
  * and r_obs < sphere_r; with the shift set and rs > 0, r_in > 1.5 rs
  * (GEO_EINVAL; GEO_ESTATE when no disk is set).  Colour only: a buffer armed by
- * geo_disk_hits_next_render or geo_disk_shift_next_render is consumed and the
- * call returns GEO_EINVAL.  A refused call launches nothing and writes nothing.
+ * geo_disk_hits_next_render, geo_disk_shift_next_render or
+ * geo_disk_emission_next_render is consumed and the call returns GEO_EINVAL.
+ * While geo_set_disk_emission is set the call returns GEO_EINVAL (batched
+ * emission frames are a follow-up; the one-frame entry points draw them).  A
+ * refused call launches nothing and writes nothing.
  * The executed steps of all frames go to steps_total or, with
  * GEO_FLAG_DEFER_STEPS, to the context's accumulator; geo_time_next_render and
  * the dispatch order work as for the other batches (frame 0 records the tile
@@ -462,8 +524,10 @@ int geo_render_disk_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene
  * share the integration kind (geo_render_band_set_batch's rules), else
  * GEO_EINVAL.  With GEO_FLAG_DISK, geo_render_disk_batch's rules hold for every
  * frame's scene.  GEO_ESTATE when no sky, or no disk for a disk scene, is set.
- * Colour only: a buffer armed by geo_disk_hits_next_render or
- * geo_disk_shift_next_render is consumed and the call returns GEO_EINVAL.  The
+ * Colour only: a buffer armed by geo_disk_hits_next_render,
+ * geo_disk_shift_next_render or geo_disk_emission_next_render is consumed and
+ * the call returns GEO_EINVAL.  A GEO_FLAG_DISK scene is GEO_EINVAL while
+ * geo_set_disk_emission is set (as for geo_render_disk_batch).  The
  * one-frame supersampled render's size limits apply: width and height at most
  * 2^19 (and twice a band layout's rows within what the call takes as rows).  A
  * refused call launches nothing and writes nothing; ctx, frames, scenes or

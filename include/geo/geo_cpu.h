@@ -76,6 +76,22 @@ int geo_render_cpu_disk_shift(const geo_frame* frame, const geo_scene* scene, co
                               const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h,
                               float* out_hits, const geo_disk_shift* shift, float* out_g);
 
+/* geo_render_cpu_disk with the emission of geo_set_disk_emission (geo.h):
+ * emission NULL draws the unshaded disk (ramp and n are then ignored);
+ * otherwise its fields, the ramp (n RGBA8 entries, host), n and the
+ * r_in > 1.5 rs rule are checked as the device checks them.  out_g and out_q
+ * (optional, host): nrows*width*3 floats each, the layouts of
+ * geo_disk_shift_next_render and geo_disk_emission_next_render, written only
+ * when emission is given.  GEO_FLAG_SS4 under the device's rules (out_g and
+ * out_q must then be NULL).  Output equal to the GPU's bit for bit. */
+int geo_render_cpu_disk_emission(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                 uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
+                                 uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                                 uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                                 unsigned long long* steps_total, const geo_disk* disk, const uint8_t* disk_rgba8,
+                                 uint32_t disk_w, uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                 const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,6 +299,23 @@ struct ThinDisk {
         shifted = false;
         return *this;
     }
+    // Blackbody emission (geo_set_disk_emission): off unless set_emission is
+    // called; ramp: 2..GEO_DISK_RAMP_MAX RGBA8 entries evenly spaced in 1/T from
+    // t_lo to t_hi.  While it is on it takes the shading's place.
+    bool emitting = false;
+    geo_disk_emission emission{1, GEO_DISK_PROFILE_THIN, 1.0f, 1.0f, 2.0f, 1.0f};
+    std::vector<uint8_t> ramp;
+    ThinDisk& set_emission(const std::vector<uint8_t>& ramp_rgba8, float t_ref, float t_lo, float t_hi,
+                           uint32_t profile = GEO_DISK_PROFILE_THIN, float exposure = 1.0f, int32_t spin = 1) {
+        emission = geo_disk_emission{spin, profile, t_ref, t_lo, t_hi, exposure};
+        ramp = ramp_rgba8;
+        emitting = true;
+        return *this;
+    }
+    ThinDisk& clear_emission() {
+        emitting = false;
+        return *this;
+    }
 };
 
 // ---- BasicSphereBuffer (basic_sphere_buffer.rs) -------------------------
@@ -348,6 +365,9 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
         const geo_disk gd{d.r_in, d.r_out, {d.normal.x, d.normal.y, d.normal.z}, {d.axis.x, d.axis.y, d.axis.z}};
         check(geo_set_disk(ctx_->get(), &gd, d.texture.rgba.data(), d.texture.width, d.texture.height), "geo_set_disk");
         check(geo_set_disk_shift(ctx_->get(), d.shifted ? &d.shift : nullptr), "geo_set_disk_shift");
+        check(geo_set_disk_emission(ctx_->get(), d.emitting ? &d.emission : nullptr, d.ramp.data(),
+                                    (uint32_t)(d.ramp.size() / 4u)),
+              "geo_set_disk_emission");
         disk_ = true;
     }
 

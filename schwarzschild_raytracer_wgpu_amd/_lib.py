@@ -38,6 +38,11 @@ GEO_RING_X = 5e-3
 GEO_MAX_BATCH_FRAMES = 8
 GEO_HAS_DISK_BATCH = 1  # geo_render_disk_batch
 GEO_HAS_SS4_BATCH = 1  # geo_render_ss_batch
+GEO_HAS_DISK_EMISSION = 1  # geo_set_disk_emission, geo_disk_emission_next_render
+GEO_DISK_PROFILE_POWER = 0
+GEO_DISK_PROFILE_THIN = 1
+GEO_DISK_RAMP_MAX = 1024
+GEO_DISK_G_MAX = 16.0
 
 GEO_RAYS_NEAR = 1
 GEO_RAYS_FAR = 2
@@ -94,6 +99,19 @@ class GeoDiskShift(ctypes.Structure):
     ]
 
 
+class GeoDiskEmission(ctypes.Structure):
+    """geo_disk_emission: blackbody emission of the disk (geo_set_disk_emission)."""
+
+    _fields_ = [
+        ("spin", ctypes.c_int32),
+        ("profile", ctypes.c_uint32),
+        ("t_ref", ctypes.c_float),
+        ("t_lo", ctypes.c_float),
+        ("t_hi", ctypes.c_float),
+        ("exposure", ctypes.c_float),
+    ]
+
+
 assert ctypes.sizeof(GeoFrame) == 208
 assert ctypes.sizeof(GeoScene) == 32
 
@@ -114,6 +132,8 @@ SIGNATURES = {
     "geo_disk_hits_next_render": (_int, [_vp, _vp]),
     "geo_set_disk_shift": (_int, [_vp, ctypes.POINTER(GeoDiskShift)]),
     "geo_disk_shift_next_render": (_int, [_vp, _vp]),
+    "geo_set_disk_emission": (_int, [_vp, ctypes.POINTER(GeoDiskEmission), _vp, _u32]),
+    "geo_disk_emission_next_render": (_int, [_vp, _vp]),
     "geo_set_fan": (_int, [_vp, _vp, _u32]),
     "geo_solve_ray_fan": (_int, [_vp, _f64, _f64, _u32, _f64, _u32, _f64, _vp, _vp]),
     "geo_render_rows": (

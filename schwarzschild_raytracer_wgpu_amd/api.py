@@ -117,6 +117,7 @@ class Context:
         check("geo_ctx_create", lib.geo_ctx_create(device, ctypes.byref(h)))
         self._h = h
         self.device = device
+        self.disk_emission_set = False  # set_disk_emission is on (dist.ShardedFrame asks)
 
     def close(self) -> None:
         h = getattr(self, "_h", None)
@@ -146,6 +147,7 @@ class Context:
 
     def clear_disk(self) -> None:
         check("geo_clear_disk", lib.geo_clear_disk(self._h))
+        self.disk_emission_set = False
 
     def disk_hits_next_render(self, buf) -> None:
         """geo_disk_hits_next_render: the next render writes 3 x (r, U) floats per pixel
@@ -178,6 +180,35 @@ class Context:
         if buf.dtype != torch.float32:
             raise ValueError("buf must be float32")
         check("geo_disk_shift_next_render", lib.geo_disk_shift_next_render(self._h, _ptr(buf)))
+
+    def set_disk_emission(self, ramp: np.ndarray, t_ref: float, t_lo: float, t_hi: float,
+                          profile: int = _lib.GEO_DISK_PROFILE_THIN, exposure: float = 1.0, spin: int = 1) -> None:
+        """geo_set_disk_emission: colour the disk's hits by the observed temperature
+        T_obs = g * t_ref * tau(r) (`profile`: GEO_DISK_PROFILE_POWER or _THIN) through `ramp`, an
+        (n, 4) uint8 colour ramp evenly spaced in 1/T from t_lo to t_hi (scenes.blackbody_ramp),
+        times min(exposure * (T_obs/t_ref)**4, 65536).  Takes the place of set_disk_shift while
+        set; kept across set_disk, cleared by clear_disk or clear_disk_emission."""
+        a = np.ascontiguousarray(ramp, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("ramp must be an (n, 4) uint8 array")
+        em = _lib.GeoDiskEmission(spin, profile, t_ref, t_lo, t_hi, exposure)
+        check("geo_set_disk_emission", lib.geo_set_disk_emission(self._h, ctypes.byref(em), a.ctypes.data, a.shape[0]))
+        self.disk_emission_set = True
+
+    def clear_disk_emission(self) -> None:
+        check("geo_set_disk_emission", lib.geo_set_disk_emission(self._h, None, None, 0))
+        self.disk_emission_set = False
+
+    def disk_emission_next_render(self, buf) -> None:
+        """geo_disk_emission_next_render: the next render, if it is an emission render, writes
+        the 3 q = T_obs/t_ref slots of every pixel of its rows into `buf` (a contiguous float32
+        device tensor; the caller sizes it nrows*width*3)."""
+        _check_buffer("buf", buf, 0, None)
+        import torch
+
+        if buf.dtype != torch.float32:
+            raise ValueError("buf must be float32")
+        check("geo_disk_emission_next_render", lib.geo_disk_emission_next_render(self._h, _ptr(buf)))
 
     def set_fan(self, fan: np.ndarray) -> None:
         a = np.ascontiguousarray(fan, dtype=np.float32)

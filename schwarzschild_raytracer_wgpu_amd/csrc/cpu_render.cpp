@@ -51,6 +51,11 @@ struct CpuJob {
     bool shift;
     geo::DiskShift sk;
     float* gs;
+    // geo_render_cpu_disk_emission: the emission's constants, its ramp and the optional q slots
+    bool emit;
+    geo::DiskEmission ek;
+    const uint32_t* ramp;
+    float* qs;
 };
 
 float geodesic(const CpuJob& j, float st, float ct, float rct, uint32_t* n) {
@@ -170,7 +175,7 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
         const uint32_t py = j.row0 + ly * j.row_step;
         for (uint32_t px = 0; px < j.width; ++px) {
             float c2x, c2y, c2z, g_obs = 1.0f;
-            if (j.shift)
+            if (j.shift || j.emit)
                 geo::pixel_central_dir_g(j.cam, j.f->movement_to_central, psi_k, j.kt, px, py, &c2x, &c2y, &c2z,
                                          &g_obs);
             else
@@ -195,7 +200,14 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             const size_t o = (size_t)ly * j.width + px;
             const uint32_t base = bh ? geo::kBlackRGBA : geo::sample_sky(fetch, j.sw, j.sh, j.opaque, U, V);
             float* const hits = j.hits ? j.hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
-            if (j.shift) {
+            if (j.emit) {
+                auto rfetch = [p = j.ramp](uint32_t i) { return p[i]; };
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(j.dk, j.ek.s, dr, ct, g_obs, &sr);
+                j.rgba[o] = geo::disk_shade_emit(j.dk, k, dr, j.ek, sr, Uk, n, ang, base, dsample, rfetch, hits,
+                                                 j.gs ? j.gs + o * geo::kDiskMaxCrossings : nullptr,
+                                                 j.qs ? j.qs + o * geo::kDiskMaxCrossings : nullptr);
+            } else if (j.shift) {
                 geo::DiskShiftRay sr;
                 geo::disk_shift_ray(j.dk, j.sk, dr, ct, g_obs, &sr);
                 j.rgba[o] = geo::disk_shade_shift(j.dk, k, dr, j.sk, sr, Uk, n, ang, base, dsample, hits,
@@ -308,7 +320,8 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
                     uint32_t nrows, uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
                     float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, const geo_disk* disk,
                     const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits,
-                    const geo_disk_shift* shift, float* out_g) {
+                    const geo_disk_shift* shift, float* out_g, const geo_disk_emission* emission = nullptr,
+                    const uint8_t* ramp_rgba8 = nullptr, uint32_t ramp_n = 0, float* out_q = nullptr) {
     if (!frame || !scene || !sky_rgba8 || !out_rgba8 || sky_w == 0 || sky_h == 0 || width == 0 || height == 0 ||
         row_step == 0 || width > (1u << 20) || height > (1u << 20))
         return GEO_EINVAL;
@@ -328,7 +341,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     const bool ss = (scene->flags & GEO_FLAG_SS4) != 0;
     if (ss && (scene->mode != GEO_MODE_DIRECT ||
                (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || out_mask || out_uv ||
-               out_steps || out_hits || out_g || width > (1u << 19) || height > (1u << 19)))
+               out_steps || out_hits || out_g || out_q || width > (1u << 19) || height > (1u << 19)))
         return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
@@ -349,6 +362,16 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
         if (shift && ((shift->spin != 1 && shift->spin != -1) || shift->exponent > 4u || !(shift->gain > 0.0f) ||
                       !(shift->gain <= 3.4028234e38f) || (scene->rs > 0.0f && !(disk->r_in > 1.5f * scene->rs))))
             return GEO_EINVAL;
+        // geo_set_disk_emission's rules and the render's r_in > 1.5 rs
+        if (emission) {
+            const auto pos = [](float v) { return v > 0.0f && v <= 3.4028234e38f; };  // finite, > 0
+            const geo_disk_emission* e = emission;
+            if ((e->spin != 1 && e->spin != -1) ||
+                (e->profile != GEO_DISK_PROFILE_POWER && e->profile != GEO_DISK_PROFILE_THIN) || !pos(e->t_ref) ||
+                !pos(e->t_lo) || !pos(e->t_hi) || !pos(e->exposure) || !(e->t_lo < e->t_hi) || !ramp_rgba8 ||
+                ramp_n < 2u || ramp_n > GEO_DISK_RAMP_MAX || (scene->rs > 0.0f && !(disk->r_in > 1.5f * scene->rs)))
+                return GEO_EINVAL;
+        }
     }
     if (scene->mode == GEO_MODE_FAN && (!fan || n_fan < 2)) return GEO_EINVAL;
     if (scene->mode != GEO_MODE_FAN &&
@@ -401,6 +424,19 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.shift = disk && shift;
     j.gs = out_g;
     if (j.shift) j.sk = geo::disk_shift_consts(frame->central_to_uv, scene->rs, scene->r_obs, shift->spin, shift->exponent, shift->gain);
+    j.emit = disk && emission;
+    j.qs = out_q;
+    j.ramp = nullptr;
+    std::vector<uint32_t> ramp;
+    if (j.emit) {
+        j.shift = false;
+        j.ek = geo::disk_emission_consts(frame->central_to_uv, scene->rs, scene->r_obs, emission->spin,
+                                         emission->profile, emission->t_ref, emission->t_lo, emission->t_hi,
+                                         emission->exposure, ramp_n);
+        ramp.resize(ramp_n);
+        std::memcpy(ramp.data(), ramp_rgba8, (size_t)ramp_n * 4u);
+        j.ramp = ramp.data();
+    }
     std::vector<uint32_t> dtex;
     if (disk) {
         if (!geo::disk_consts(frame->central_to_uv, disk->normal, disk->axis, disk->r_in, disk->r_out, j.k, &j.dk))
@@ -481,4 +517,21 @@ extern "C" int geo_render_cpu_disk_shift(const geo_frame* frame, const geo_scene
     return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
                            disk_h, out_hits, shift, shift || ss ? out_g : nullptr);
+}
+
+extern "C" int geo_render_cpu_disk_emission(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                            uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                            uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                            uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                            float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                            const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                            uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                            const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q) {
+    if (!disk) return GEO_EINVAL;
+    // (GEO_FLAG_SS4 is colour only: out_g and out_q refuse the call whether they would be written or not)
+    const bool ss = scene && (scene->flags & GEO_FLAG_SS4) != 0;
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, nullptr, emission || ss ? out_g : nullptr, emission, ramp_rgba8, n,
+                           emission || ss ? out_q : nullptr);
 }

@@ -115,6 +115,16 @@ struct geo_ctx {
     bool shift_set;
     geo_disk_shift shift;
     float* g_next;
+    // geo_set_disk_emission: the blackbody emission (kept across geo_set_disk,
+    // cleared by geo_clear_disk), its ramp of emit_n RGBA8 entries (a device
+    // buffer of GEO_DISK_RAMP_MAX entries, allocated by the first set and kept
+    // to the context's end) and the q buffer of geo_disk_emission_next_render
+    // (the next render's alone)
+    bool emit_set;
+    geo_disk_emission emit;
+    uint32_t* emit_ramp;
+    uint32_t emit_n;
+    float* q_next;
 #if defined(GEO_WAVE_LOG)
     unsigned long long* wave_log;  // diagnostic build only (geo_debug_set_wave_log)
 #endif

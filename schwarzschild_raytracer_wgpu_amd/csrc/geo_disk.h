@@ -455,4 +455,137 @@ GEO_HD uint32_t disk_shade_shift(const DiskConsts& d, const PixelConsts& k, cons
     return c;
 }
 
+// ---- Blackbody emission (geo_set_disk_emission) ---------------------------
+// The disk's colour from a temperature: a radial profile T(r) = t_ref tau(r),
+// the observed temperature T_obs = g T(r) with the g of the shading above (the
+// emission's own spin), a colour ramp over 1/T_obs and the bolometric
+// brightness (T_obs / t_ref)^4, which holds the g^4 beaming.
+//   tau(r), x = r_in / r:
+//     GEO_DISK_PROFILE_POWER  x^(3/4)
+//     GEO_DISK_PROFILE_THIN   x^(3/4) (1 - sqrt x)^(1/4) / f_max, the zero-torque
+//       inner edge; f_max = (6/7)^(3/2) (1/7)^(1/4) = 0.487871339, reached at
+//       x = 36/49: tau = 0 at r_in, 1 at r = 49/36 r_in
+// The f32 specification (the operations of geo_math.h / geo_pixel.h; no
+// hardware log, exp or pow):
+//   per frame (host, f64, each rounded once): sb, ih = disk_shift_consts with
+//     the emission's spin;  inv_fmax = 1 / ((6/7)^1.5 (1/7)^0.25);
+//     D = 1/t_lo - 1/t_hi;  ka = -(n - 1) / (t_ref D);  kb = (n - 1) (1/t_lo) / D;
+//     n1 = n - 1 (exact)
+//   per ray: disk_shift_ray, unchanged
+//   per hit (r of disk_hit, g of disk_shift_g):
+//     ir = rcpf_(r);  x = med3(r_in ir, 0, 1) (r can round an ulp under r_in:
+//       1 - sqrt x must not go negative);  s = sqrtf_(x);  tau = s sqrtf_(s);
+//     THIN: tau = min((tau sqrtf_(sqrtf_(1 - s))) inv_fmax, 1);
+//     q = g tau;  q2 = q q;  m = min(exposure (q2 q2), 65536);
+//     pos = med3(fma(rcpf_(q), ka, kb), 0, n1)  (q = 0: rcpf_ = +inf, ka < 0,
+//       so -inf, which clamps to 0; a NaN clamps to 0 as well);
+//     i = min((uint32_t)floor_i32_(pos), n - 2);  w = floor_i32_((pos - i) 256)
+//   ramp colour e, per channel of entries a = ramp[i], b = ramp[i + 1]:
+//     (a (256 - w) + b w + 128) >> 8  (w in 0..256; pos = n - 1 gives i = n - 2
+//     and w = 256: the last entry exactly)
+//   colour: mk = m (1/255) (kInv255, f32);  each of R, G, B of the hit's texture
+//     sample t: min(255, floor_i32_(fma((float)(t_c e_c), mk, 0.5)));  alpha kept.
+// Ranges: q <= GEO_DISK_G_MAX = 16, so q^4 <= 65536 = the cap of m;
+// t_c e_c <= 65025 and 65025 * 65536 / 255 = 16711680 < 2^24, inside
+// floor_i32_'s range and exact as an integer-valued f32 bound.
+constexpr float kInv255 = 1.0f / 255.0f;
+constexpr uint32_t kDiskProfilePower = 0u, kDiskProfileThin = 1u;  // GEO_DISK_PROFILE_*
+constexpr uint32_t kDiskRampMax = 1024u;                           // GEO_DISK_RAMP_MAX
+
+struct DiskEmission {
+    DiskShift s;  // sb and ih with the emission's spin (gain and exponent unused)
+    float inv_fmax;
+    float ka, kb;
+    float n1;  // n - 1
+    float exposure;
+    uint32_t profile;
+    uint32_t n2;  // n - 2
+};
+
+// m2, rs, r_obs, spin: disk_shift_consts's; 0 < t_lo < t_hi, t_ref > 0, n in 2..kDiskRampMax.
+GEO_HD DiskEmission disk_emission_consts(const float* m2, float rs, float r_obs, int spin, uint32_t profile,
+                                         float t_ref, float t_lo, float t_hi, float exposure, uint32_t n) {
+    DiskEmission e;
+    e.s = disk_shift_consts(m2, rs, r_obs, spin, 0u, 1.0f);
+    e.inv_fmax = (float)(1.0 / (__builtin_sqrt(6.0 / 7.0) * (6.0 / 7.0) * __builtin_sqrt(__builtin_sqrt(1.0 / 7.0))));
+    const double il = 1.0 / (double)t_lo, D = il - 1.0 / (double)t_hi, n1 = (double)(n - 1u);
+    e.ka = (float)(-n1 / ((double)t_ref * D));
+    e.kb = (float)(n1 * il / D);
+    e.n1 = (float)(n - 1u);
+    e.exposure = exposure;
+    e.profile = profile;
+    e.n2 = n - 2u;
+    return e;
+}
+
+// q = T_obs / t_ref of a hit at radius r seen at the frequency ratio g.
+GEO_HD float disk_emission_q(const DiskConsts& d, const DiskEmission& e, float g, float r) {
+    const float ir = rcpf_(r);
+    const float x = med3_(d.r_in * ir, 0.0f, 1.0f);
+    const float s = sqrtf_(x);
+    float tau = s * sqrtf_(s);
+    if (e.profile == kDiskProfileThin)  // frame-uniform
+        tau = __builtin_fminf((tau * sqrtf_(sqrtf_(1.0f - s))) * e.inv_fmax, 1.0f);
+    return g * tau;
+}
+
+// The texture sample smp shaded by the ramp's colour at q (alpha kept).
+// fetch(i): entry i of the ramp, i < n.
+template <typename Fetch>
+GEO_HD uint32_t disk_emission_colour(const DiskEmission& e, float q, uint32_t smp, const Fetch& fetch) {
+    const float q2 = q * q;
+    const float m = __builtin_fminf(e.exposure * (q2 * q2), kDiskMMax);
+    const float pos = med3_(fmaf_(rcpf_(q), e.ka, e.kb), 0.0f, e.n1);
+    const uint32_t fi = (uint32_t)floor_i32_(pos);
+    const uint32_t i = fi < e.n2 ? fi : e.n2;  // (unsigned: whatever pos is, i + 1 < n)
+    const uint32_t w = (uint32_t)floor_i32_((pos - (float)i) * 256.0f);
+    const uint32_t a = fetch(i), b = fetch(i + 1u);
+    const uint32_t iw = 256u - w;
+    // R and B in 16-bit fields (a field is at most 255 * 256 + 128: no carry), G alone
+    const uint32_t rb = (((a & 0x00FF00FFu) * iw + (b & 0x00FF00FFu) * w + 0x00800080u) >> 8) & 0x00FF00FFu;
+    const uint32_t gg = (((a >> 8) & 0xFFu) * iw + ((b >> 8) & 0xFFu) * w + 128u) >> 8;
+    const float mk = m * kInv255;
+    return disk_shift_channel_((smp & 0xFFu) * (rb & 0xFFu), mk) |
+           (disk_shift_channel_(((smp >> 8) & 0xFFu) * gg, mk) << 8) |
+           (disk_shift_channel_(((smp >> 16) & 0xFFu) * (rb >> 16), mk) << 16) | (smp & 0xFF000000u);
+}
+
+// disk_shade_shift_slot_ with the emission: qs (optional): the pixel's 3 q
+// slots (0 where the crossing is no hit).
+template <int S, typename Sample, typename Fetch>
+GEO_HD uint32_t disk_shade_emit_slot_(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr,
+                                      const DiskEmission& em, const DiskShiftRay& sr, float Us, uint32_t steps,
+                                      float angle, uint32_t c, const Sample& sample, const Fetch& fetch, float* hits,
+                                      float* gs, float* qs) {
+    float r = 0.0f, Ud = 0.0f, Vd = 0.0f, g = 0.0f, q = 0.0f;
+    if (disk_hit(d, k, dr, S, Us, steps, angle, &r, &Ud, &Vd)) {
+        g = disk_shift_g(k, sr, r);
+        q = disk_emission_q(d, em, g, r);
+        c = composite_(disk_emission_colour(em, q, sample(Ud, Vd), fetch), c);
+    } else {
+        r = 0.0f;
+        Ud = 0.0f;
+    }
+    if (hits) {
+        hits[2 * S] = r;
+        hits[2 * S + 1] = Ud;
+    }
+    if (gs) gs[S] = g;
+    if (qs) qs[S] = q;
+    return c;
+}
+
+template <typename Sample, typename Fetch>
+GEO_HD uint32_t disk_shade_emit(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr, const DiskEmission& em,
+                                const DiskShiftRay& sr, const float (&Uk)[kDiskMaxCrossings], uint32_t steps,
+                                float angle, uint32_t base, const Sample& sample, const Fetch& fetch, float* hits,
+                                float* gs, float* qs) {
+    static_assert(kDiskMaxCrossings == 3, "three slots, written out");
+    uint32_t c = base;
+    c = disk_shade_emit_slot_<2>(d, k, dr, em, sr, Uk[2], steps, angle, c, sample, fetch, hits, gs, qs);
+    c = disk_shade_emit_slot_<1>(d, k, dr, em, sr, Uk[1], steps, angle, c, sample, fetch, hits, gs, qs);
+    c = disk_shade_emit_slot_<0>(d, k, dr, em, sr, Uk[0], steps, angle, c, sample, fetch, hits, gs, qs);
+    return c;
+}
+
 }  // namespace geo

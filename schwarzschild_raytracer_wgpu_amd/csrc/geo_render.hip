@@ -161,6 +161,7 @@ void geo_ctx_destroy(geo_ctx* c) {
         if (c->step_set_rec[i]) (void)hipEventSynchronize(c->step_set_free[i]);
     if (c->sky) (void)hipFree(c->sky);
     if (c->disk_tex) (void)hipFree(c->disk_tex);
+    if (c->emit_ramp) (void)hipFree(c->emit_ramp);
     for (int b = 0; b < 2; ++b) {
         if (c->fan[b]) (void)hipFree(c->fan[b]);
         (void)hipEventDestroy(c->fan_written[b]);
@@ -256,6 +257,7 @@ int geo_clear_disk(geo_ctx* c) {
     c->disk_tex = nullptr;
     c->disk_set = false;
     c->shift_set = false;
+    c->emit_set = false;
     return GEO_OK;
 }
 
@@ -324,6 +326,41 @@ int geo_set_disk_shift(geo_ctx* c, const geo_disk_shift* shift) {
 int geo_disk_shift_next_render(geo_ctx* c, float* out_g) {
     if (!c || !out_g) return GEO_EINVAL;
     c->g_next = out_g;
+    return GEO_OK;
+}
+
+int geo_set_disk_emission(geo_ctx* c, const geo_disk_emission* e, const uint8_t* ramp_rgba8, uint32_t n) {
+    if (!c) return GEO_EINVAL;
+    if (!e) {
+        c->emit_set = false;
+        return GEO_OK;
+    }
+    const auto pos = [](float v) { return v > 0.0f && v <= 3.4028234e38f; };  // finite, > 0
+    if ((e->spin != 1 && e->spin != -1) || (e->profile != GEO_DISK_PROFILE_POWER && e->profile != GEO_DISK_PROFILE_THIN) ||
+        !pos(e->t_ref) || !pos(e->t_lo) || !pos(e->t_hi) || !pos(e->exposure) || !(e->t_lo < e->t_hi) || !ramp_rgba8 ||
+        n < 2u || n > GEO_DISK_RAMP_MAX)
+        return GEO_EINVAL;
+    DeviceGuard g(c->device);
+    if (!g.ok) return GEO_EHIP;
+    // renders in flight may read the current ramp (geo_set_disk's rule)
+    if (wait_renders(c) != GEO_OK) return GEO_EHIP;
+    if (!c->emit_ramp && hipMalloc(&c->emit_ramp, GEO_DISK_RAMP_MAX * sizeof(uint32_t)) != hipSuccess) {
+        c->emit_ramp = nullptr;
+        return GEO_ENOMEM;
+    }
+    if (hipMemcpy(c->emit_ramp, ramp_rgba8, (size_t)n * 4u, hipMemcpyHostToDevice) != hipSuccess) {
+        c->emit_set = false;  // the buffer's contents are unknown now: no emission
+        return GEO_EHIP;
+    }
+    c->emit = *e;
+    c->emit_n = n;
+    c->emit_set = true;
+    return GEO_OK;
+}
+
+int geo_disk_emission_next_render(geo_ctx* c, float* out_q) {
+    if (!c || !out_q) return GEO_EINVAL;
+    c->q_next = out_q;
     return GEO_OK;
 }
 
@@ -545,18 +582,24 @@ static void fill_disk_tex(const geo_ctx* c, D& d) {
 }
 
 // A GEO_FLAG_DISK frame on the wave-block grid: geo_render_disk_kernel, or the
-// shifted render (geo_render_disk_shift_kernel) with its constants *sh.
+// shifted render (geo_render_disk_shift_kernel) with its constants *sh, or the
+// emission render (geo_render_disk_emit_kernel) with *em.
 static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskShiftArgs) <= 4096,
+              "kernel arguments fit 4 KiB");
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskEmitArgs) <= 4096,
               "kernel arguments fit 4 KiB");
 template <int KIND>
 static int launch_disk(const RenderArgs& a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh,
-                       const LaunchPlan& p) {
+                       const DiskEmitArgs* em, const LaunchPlan& p) {
     FrameBatch<1> fb;
     fb.f[0] = fk;
     return launch_split(a, p, wave_block_max_ny(p.tiles_x),
                         [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
         const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
-        if (sh)
+        if (em)
+            hipExtLaunchKernelGGL(geo_render_disk_emit_kernel<KIND>, grid, block, 0, p.s, start, stop, 0, la, fb, d,
+                                  *em);
+        else if (sh)
             hipExtLaunchKernelGGL(geo_render_disk_shift_kernel<KIND>, grid, block, 0, p.s, start, stop, 0, la, fb, d,
                                   *sh);
         else
@@ -626,6 +669,7 @@ static int invalid_call(geo_ctx* c) {
         c->time_start = c->time_stop = nullptr;
         c->hits_next = nullptr;
         c->g_next = nullptr;
+        c->q_next = nullptr;
     }
     return GEO_EINVAL;
 }
@@ -657,8 +701,10 @@ struct RenderCall {
 
 // What the stages of a render call (render_impl) hand on.
 struct RenderWork {
-    float* out_hits;  // geo_disk_hits_next_render's buffer, geo_disk_shift_next_render's
-    float* out_g;
+    float* out_hits;  // geo_disk_hits_next_render's buffer, geo_disk_shift_next_render's,
+    float* out_g;     // geo_disk_emission_next_render's
+    float* out_q;
+    bool emit;  // a GEO_FLAG_DISK scene with the emission set (check_scene)
     bool disk, ring_flag, mips, adaptive, defer;  // what the scene asks for (check_scene)
     bool ss;  // GEO_FLAG_SS4: the kernels' frame is the sample frame, twice the call's in width, height and rows
     bool ring;                                    // ring_flag and a capture orbit to draw (fill_frames)
@@ -691,7 +737,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && rc.nframes != 1) ||
                  scene->mode != GEO_MODE_DIRECT ||
                  (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
-                 rc.out_uv || rc.out_steps || w.out_hits || w.out_g || rc.width > (1u << 19) ||
+                 rc.out_uv || rc.out_steps || w.out_hits || w.out_g || w.out_q || rc.width > (1u << 19) ||
                  rc.height > (1u << 19)))
         return GEO_EINVAL;
     // geo_render_ss_batch draws SS4 scenes only (the other batched calls draw the rest)
@@ -704,7 +750,11 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
         return GEO_EINVAL;
     // geo_render_disk_batch draws disk scenes only, and colour only: an armed
     // per-pixel buffer (consumed by render_impl) refuses the call
-    if (rc.disk_batch && (!w.disk || w.out_hits || w.out_g)) return GEO_EINVAL;
+    if (rc.disk_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
+    // geo_set_disk_emission: the one-frame entry points only (a batched disk
+    // frame would come out without its emission: refused, nothing launched)
+    w.emit = w.disk && c->emit_set;
+    if (w.emit && (rc.disk_batch || rc.ss_batch)) return GEO_EINVAL;
     w.ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (w.ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
         return GEO_EINVAL;
@@ -733,7 +783,8 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
             !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
             return GEO_EINVAL;
         // shading: circular timelike orbits down to the inner edge
-        if (c->shift_set && scene->rs > 0.0f && !(c->disk.r_in > 1.5f * scene->rs)) return GEO_EINVAL;
+        if ((c->shift_set || c->emit_set) && scene->rs > 0.0f && !(c->disk.r_in > 1.5f * scene->rs))
+            return GEO_EINVAL;
     }
     return GEO_OK;
 }
@@ -861,9 +912,11 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     }
     if (c->dispatch_mode != GEO_DISPATCH_LONGEST_FIRST) return GEO_OK;
     // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost
-    // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's)
+    // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's; an
+    // emission render has a key of its own, as the disk render has)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
-                             (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u),
+                             (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u) |
+                                 (w.emit ? 16u : 0u),
                              tiles_x * tiles_y};
     if (!c->learn_valid || std::memcmp(key, c->learn_key, sizeof(key)) != 0) {
         std::memcpy(c->learn_key, key, sizeof(key));
@@ -929,6 +982,19 @@ static int launch_fan(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     return GEO_OK;
 }
 
+// The emission's kernel argument for frame 0 of the call (the emission takes
+// the shift's place: geo_set_disk_shift's state is not read).
+static DiskEmitArgs emit_args(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    DiskEmitArgs em;
+    em.k = geo::disk_emission_consts(rc.frames[0].central_to_uv, rc.scene->rs, rc.scene->r_obs, c->emit.spin,
+                                     c->emit.profile, c->emit.t_ref, c->emit.t_lo, c->emit.t_hi, c->emit.exposure,
+                                     c->emit_n);
+    em.ramp = c->emit_ramp;
+    em.out_g = w.out_g;
+    em.out_q = w.out_q;
+    return em;
+}
+
 // Stage 5, a GEO_FLAG_DISK frame drawn alone.
 static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskArgs d;
@@ -943,16 +1009,20 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
                                       c->shift.exponent, c->shift.gain);
         sh.out_g = w.out_g;
     }
+    DiskEmitArgs em;
+    if (w.emit) em = emit_args(c, rc, w);
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        return launch_disk<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr, w.p);
+        return launch_disk<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
+                                                  w.emit ? &em : nullptr, w.p);
     });
 }
 
-// Stage 5, a GEO_FLAG_SS4 frame: the plain frame, the disk frame or the shifted
-// disk frame, the disk's constants as launch_disk_frame derives them (they do
+// Stage 5, a GEO_FLAG_SS4 frame: the plain frame, the disk frame, the shifted
+// disk frame or the emission frame, the disk's constants as launch_disk_frame derives them (they do
 // not depend on the resolution).
 static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(SsArgs<kSsDiskShift>) <= 4096,
               "kernel arguments fit 4 KiB");
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(SsEmitArgs) <= 4096, "kernel arguments fit 4 KiB");
 static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     SsArgs<kSsDiskShift> x;
     x.out_width = rc.width;
@@ -980,6 +1050,13 @@ static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderW
                 xp.out_width = x.out_width;
                 hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsPlain>), grid, block, 0, w.p.s, start, stop, 0, la,
                                       fb, xp);
+            } else if (w.emit) {
+                SsEmitArgs xe;
+                xe.out_width = x.out_width;
+                xe.d = x.d;
+                xe.em = emit_args(c, rc, w);  // (SS4 is colour only: out_g and out_q are null here)
+                hipExtLaunchKernelGGL(geo_render_ss_emit_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0, la, fb,
+                                      xe);
             } else if (!c->shift_set) {
                 SsArgs<kSsDisk> xd;
                 xd.out_width = x.out_width;
@@ -1153,6 +1230,8 @@ static int render_impl(geo_ctx* c, const RenderCall& rc) {
     c->hits_next = nullptr;
     w.out_g = c->g_next;
     c->g_next = nullptr;
+    w.out_q = c->q_next;
+    c->q_next = nullptr;
     int st = check_scene(c, rc, w);
     if (st) return st;
     DeviceGuard g(c->device);

@@ -813,6 +813,79 @@ __global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderA
     disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
 }
 
+// The emission render (geo_set_disk_emission): the shifted kernel's prologue,
+// loop and epilogue with geo::disk_shade_emit_slot_'s hit arm, which turns g
+// and r into q = T_obs / t_ref, reads the ramp's two neighbouring entries (two
+// dword loads, inside the arm only) and scales the texture sample.  A kernel
+// of its own with its own further argument, for the reason given above.
+struct DiskEmitArgs {
+    geo::DiskEmission k;
+    const uint32_t* ramp;  // k.n2 + 2 RGBA8 entries
+    float* out_g;          // optional: 3 x g per pixel
+    float* out_q;          // optional: 3 x q per pixel
+};
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                  const DiskArgs d, const DiskEmitArgs em) {
+    const FrameK& f = fb.f[0];
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    uint32_t steps = 0;
+    if (px < a.width && ly < a.nrows && py < a.height) {
+        float c2x, c2y, c2z, g_obs;
+        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                                 &c2x, &c2y, &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        geo::DiskRay dr;
+        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const size_t o = (size_t)ly * a.width + px;
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
+                                                                    kBufferRsrcWord3),
+                                  d.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
+        };
+        const auto rfetch = [ramp = em.ramp](uint32_t i) { return ramp[i]; };
+        geo::DiskShiftRay sr;
+        geo::disk_shift_ray(d.k, em.k.s, dr, ct, g_obs, &sr);
+        a.out_rgba[o] = geo::disk_shade_emit(d.k, a.k, dr, em.k, sr, Uk, steps, ang, base, dsample, rfetch,
+                                             d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr,
+                                             em.out_g ? em.out_g + o * geo::kDiskMaxCrossings : nullptr,
+                                             em.out_q ? em.out_q + o * geo::kDiskMaxCrossings : nullptr);
+        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
+        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
+        if (a.out_steps) a.out_steps[o] = steps;
+    }
+    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
+}
+
 // ---- geo_render_disk_batch: up to kMaxBatchFrames disk frames in one launch --
 // The two kernels above with the frame in blockIdx.z (its output a.out_frame_px
 // pixels after the last frame's), colour only, on the same wave-block grid.
@@ -1082,6 +1155,78 @@ __global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, c
     // Every per-lane arm (out of frame, black hole, disk hits, shading) has
     // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
     // of the frame resolves four zeros and is not stored.
+    const uint32_t resolved = ss_resolve(colour);
+    if (in_frame && (lane & 0x11u) == 0u) a.out_rgba[(size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
+    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
+}
+
+// The supersampled emission frame (geo_set_disk_emission with GEO_FLAG_SS4):
+// geo_render_ss_kernel's disk arm with geo::disk_shade_emit.  A kernel of its
+// own, not a fourth VAR of the template above: that template's body, and with
+// it the code of its nine instantiations, stays untouched.
+struct SsEmitArgs {
+    uint32_t out_width;
+    DiskArgs d;
+    DiskEmitArgs em;
+};
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_ss_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                const SsEmitArgs x) {
+    const FrameK& f = fb.f[0];
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // (the sample grid, the band index and the quad partners: geo_render_ss_kernel's)
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // the sample's colour, kept in a register
+    if (in_frame) {
+        float c2x, c2y, c2z, g_obs;
+        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
+                                 &c2x, &c2y, &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        const DiskArgs& d = x.d;
+        geo::DiskRay dr;
+        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
+                                                                    kBufferRsrcWord3),
+                                  d.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
+        };
+        const auto rfetch = [ramp = x.em.ramp](uint32_t i) { return ramp[i]; };
+        geo::DiskShiftRay sr;
+        geo::disk_shift_ray(d.k, x.em.k.s, dr, ct, g_obs, &sr);
+        colour = geo::disk_shade_emit(d.k, a.k, dr, x.em.k, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
+                                      nullptr);
+    }
+    // (all 64 lanes are active again, as the exchange needs)
     const uint32_t resolved = ss_resolve(colour);
     if (in_frame && (lane & 0x11u) == 0u) a.out_rgba[(size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
     disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
@@ -1654,6 +1799,12 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsDiskShift>;
     (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsDiskShift>;
     (void)geo_render_ss_batch_kernel<geo::kFlat, kSsDiskShift>;
+    (void)geo_render_disk_emit_kernel<geo::kCurvedOut>;
+    (void)geo_render_disk_emit_kernel<geo::kCurvedIn>;
+    (void)geo_render_disk_emit_kernel<geo::kFlat>;
+    (void)geo_render_ss_emit_kernel<geo::kCurvedOut>;
+    (void)geo_render_ss_emit_kernel<geo::kCurvedIn>;
+    (void)geo_render_ss_emit_kernel<geo::kFlat>;
 }
 
 }  // namespace

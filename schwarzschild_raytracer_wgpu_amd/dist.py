@@ -249,6 +249,8 @@ class ShardedFrame:
         self.batch = bool(batch_launch) and self.K > 1
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
+        if self.batch:
+            self._refuse_emission_batch(scene)
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
         self.pending_scenes = []     # and copies of their scenes (they differ in r_obs at most)
         self._pending_key = b""
@@ -333,6 +335,16 @@ class ShardedFrame:
         k = (i // self.K) % 2 % self.S if self.batch else i % self.S
         return self.stream0 if k == 0 else self.extra[k - 1]
 
+    def _refuse_emission_batch(self, scene) -> None:
+        """The batched entry points draw no emission frames (geo_set_disk_emission,
+        geo.h): a GEO_FLAG_DISK scene of a context with the emission set is
+        refused here, by name, instead of by the launch's GEO_EINVAL."""
+        from ._lib import GEO_FLAG_DISK
+
+        if scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_emission_set", False):
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on (batched emission frames "
+                             "are not built yet): use batch_launch=False, or clear_disk_emission()")
+
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
         """The frames of batch buffer b (slots first .. first + len(frames) - 1)
@@ -360,6 +372,7 @@ class ShardedFrame:
         # supersampled scenes (with a disk or without) and thin-disk scenes
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
+        self._refuse_emission_batch(scenes[0])
         if scenes[0].flags & GEO_FLAG_SS4:
             name = "geo_render_ss_batch"
         elif scenes[0].flags & GEO_FLAG_DISK:

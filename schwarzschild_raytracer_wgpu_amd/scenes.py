@@ -101,3 +101,44 @@ def make_disk_texture(size=(512, 64)) -> np.ndarray:
     tex[..., :3] = np.clip(np.rint(rgb), 0, 255).astype(np.uint8)
     tex[..., 3] = np.clip(np.rint(255.0 * alpha), 0, 255).astype(np.uint8)
     return tex
+
+
+def _lobe(lam: np.ndarray, mu: float, s1: float, s2: float) -> np.ndarray:
+    t = (lam - mu) / np.where(lam < mu, s1, s2)
+    return np.exp(-0.5 * t * t)
+
+
+def blackbody_xyz(temps) -> np.ndarray:
+    """(..., 3) f64 CIE 1931 XYZ (arbitrary common scale) of Planckian radiators
+    at `temps` kelvin: Planck's law over 360..830 nm in 1 nm steps, weighted by
+    the multi-lobe Gaussian fit to the CIE 1931 standard observer."""
+    T = np.asarray(temps, dtype=np.float64)[..., None]
+    lam = np.arange(360.0, 831.0, 1.0)
+    xb = 1.056 * _lobe(lam, 599.8, 37.9, 31.0) + 0.362 * _lobe(lam, 442.0, 16.0, 26.7) \
+        - 0.065 * _lobe(lam, 501.1, 20.4, 26.2)
+    yb = 0.821 * _lobe(lam, 568.8, 46.9, 40.5) + 0.286 * _lobe(lam, 530.9, 16.3, 31.1)
+    zb = 1.217 * _lobe(lam, 437.0, 11.8, 36.0) + 0.681 * _lobe(lam, 459.0, 26.0, 13.8)
+    c2 = 1.438776877e7  # h c / k_B in nm K
+    # (the spectral radiance up to a constant factor; the ramp is normalised)
+    planck = (lam / 560.0) ** -5 / np.expm1(c2 / (lam * T))
+    return np.stack([(planck * xb).sum(axis=-1), (planck * yb).sum(axis=-1), (planck * zb).sum(axis=-1)], axis=-1)
+
+
+def blackbody_ramp(n: int, t_lo: float, t_hi: float) -> np.ndarray:
+    """(n, 4) uint8 colour ramp for Context.set_disk_emission: entry i is the
+    colour of a Planckian radiator at 1/T = 1/t_lo - i/(n-1) (1/t_lo - 1/t_hi)
+    (evenly spaced in 1/T), its XYZ (blackbody_xyz) taken to linear sRGB,
+    negatives clipped, divided by its largest channel (the brightness comes from
+    the renderer's T^4 factor) and encoded with the sRGB transfer curve; alpha 255."""
+    if not (2 <= n <= 1024) or not (0.0 < t_lo < t_hi) or not math.isfinite(t_hi):
+        raise ValueError("blackbody_ramp needs 2 <= n <= 1024 and 0 < t_lo < t_hi")
+    inv = 1.0 / t_lo - np.arange(n, dtype=np.float64) / (n - 1) * (1.0 / t_lo - 1.0 / t_hi)
+    xyz = blackbody_xyz(1.0 / inv)
+    m = np.array([[3.2406, -1.5372, -0.4986], [-0.9689, 1.8758, 0.0415], [0.0557, -0.2040, 1.0570]])
+    rgb = np.clip(xyz @ m.T, 0.0, None)
+    rgb = rgb / rgb.max(axis=-1, keepdims=True)
+    enc = np.where(rgb <= 0.0031308, 12.92 * rgb, 1.055 * np.power(rgb, 1.0 / 2.4) - 0.055)
+    ramp = np.empty((n, 4), dtype=np.uint8)
+    ramp[:, :3] = np.clip(np.rint(255.0 * enc), 0, 255).astype(np.uint8)
+    ramp[:, 3] = 255
+    return ramp

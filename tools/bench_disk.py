@@ -13,11 +13,24 @@ it.
   python tools/bench_disk.py [--n 30] [--out profiles/disk_bench_cfg3.json]
   python tools/bench_disk.py --shift [--n 30] [--out profiles/disk_shift_bench_cfg3.json]
 
+  python tools/bench_disk.py --emission [--n 30] [--out profiles/disk_emission_bench_cfg3.json]
   python tools/bench_disk.py --batch 8 [--n 30] [--out profiles/disk_batch_bench_cfg3.json]
 
 --shift adds the shaded disk frame (geo_set_disk_shift: spin +1, exponent 4,
 gain 1) as a third kind in the same alternation and reports it against the
 unshaded disk frame; its output file is a JSON list that every run appends to.
+
+--emission measures the blackbody emission frame (geo_set_disk_emission: THIN
+profile, a 256-entry scenes.blackbody_ramp) against the shaded disk frame
+(--shift's), each on its own context: --alternations (5) times, --n (30)
+event-timed dispatches of the shaded frame, then as many of the emission frame
+(after --settle alternations of the same form, which are reported apart: the
+first blocks after the warm-up run slower for both kinds).
+It reports each alternation's medians and their ratio, the ratio of the
+medians over all alternations, and the shaded side's own spread over the
+alternations ((max - min) / median of its per-alternation medians): the noise
+the ratio is read against.  Its output file, profiles/disk_emission_bench_cfg3.json, is a JSON list that
+every run appends to.
 
 --batch K measures the batched disk launch (geo_render_disk_batch) where it is
 used: a peer's share of the 4K frame at N = 8 (8-row bands, BandLayout rank 1 of
@@ -45,18 +58,26 @@ def main():
     p.add_argument("--n", type=int, default=30, help="timed renders of each kind (>= 20)")
     p.add_argument("--warmup", type=int, default=40, help="untimed renders of each kind first")
     p.add_argument("--shift", action="store_true", help="also time the Doppler-shaded disk frame")
+    p.add_argument("--emission", action="store_true",
+                   help="time the blackbody emission frame against the shaded disk frame, in alternating blocks")
+    p.add_argument("--alternations", type=int, default=5, help="with --emission: blocks of --n renders of each kind")
+    p.add_argument("--settle", type=int, default=4,
+                   help="with --emission: alternations run first in the timed form, reported apart and not counted")
     p.add_argument("--batch", type=int, default=0, metavar="K",
                    help="measure one launch of K disk frames against K one-frame launches (a peer's share at N = 8)")
     p.add_argument("--out")
     args = p.parse_args()
     if not args.out:
         name = "disk_batch_bench_cfg3.json" if args.batch else (
-            "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json")
+            "disk_emission_bench_cfg3.json" if args.emission else (
+                "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json"))
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
     if args.batch:
         return batch_main(args)
+    if args.emission:
+        return emission_main(args)
 
     import numpy as np
     import torch
@@ -143,6 +164,102 @@ def main():
             with open(args.out) as f:
                 doc = json.load(f)
         doc.append(res)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(doc, indent=1) + "\n")
+
+
+def emission_main(args):
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, blackbody_ramp, make_disk_texture, make_sky
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg = CONFIGS["cfg3_4k"]
+    W, H = cfg.width, cfg.height
+    obs = g.Observer(cfg.rs, cfg.fov, W, H)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg.step, cfg.max_steps,
+                         flags=_lib.GEO_FLAG_DISK)
+    r_in, r_out = 1.6 * cfg.rs, 2.2 * cfg.rs
+    emission = dict(t_ref=9000.0, t_lo=1500.0, t_hi=30000.0, profile=_lib.GEO_DISK_PROFILE_THIN, exposure=1.0, spin=1)
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    # (each kind on its own context: the learned dispatch order is kept per context)
+    ctxs = {}
+    for kind in ("shift", "emission"):
+        c = g.Context(0)
+        c.set_sky(sky)
+        c.set_disk(tex, r_in, r_out)
+        if kind == "shift":
+            c.set_disk_shift(1, 4, 1.0)
+        else:
+            c.set_disk_emission(blackbody_ramp(256, emission["t_lo"], emission["t_hi"]), **emission)
+        ctxs[kind] = c
+    dev = torch.device("cuda:0")
+    out = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)
+    for _ in range(args.warmup):
+        for c in ctxs.values():
+            c.render_rows(frame, scene, W, H, 0, H, out)
+    torch.cuda.synchronize()
+    # The first blocks after the warm-up are slower for both kinds (a block of 30 event-timed renders of one kind
+    # back to back is another regime than the warm-up's untimed renders of alternating kinds, and the device takes
+    # about a hundred renders to settle in it): --settle alternations are run in the timed form and kept apart
+    blocks, settling = [], []
+    for alt in range(args.settle + args.alternations):
+        med = {}
+        for kind, c in ctxs.items():
+            ev = []
+            for _ in range(args.n):
+                a, b = HipEvent(), HipEvent()
+                c.time_next_render(a, b)
+                c.render_rows(frame, scene, W, H, 0, H, out)
+                ev.append((a, b))
+            torch.cuda.synchronize()
+            ms = np.array([a.elapsed_time(b) for a, b in ev])
+            med[kind + "_ms_median"] = float(np.median(ms))
+            med[kind + "_ms_min"] = float(ms.min())
+            med[kind + "_ms_iqr"] = float(np.subtract(*np.percentile(ms, [75, 25])))
+        med["emission_over_shift"] = med["emission_ms_median"] / med["shift_ms_median"]
+        (settling if alt < args.settle else blocks).append(med)
+    # what the emission frame draws (one more render, untimed)
+    q = torch.zeros(W * H * 3, dtype=torch.float32, device=dev)
+    ctxs["emission"].disk_emission_next_render(q)
+    ctxs["emission"].render_rows(frame, scene, W, H, 0, H, out)
+    torch.cuda.synchronize()
+    qv = q.view(H, W, 3)
+    hit = qv > 0
+    for c in ctxs.values():
+        c.close()
+    sm = np.array([b["shift_ms_median"] for b in blocks])
+    em = np.array([b["emission_ms_median"] for b in blocks])
+    res = {
+        "config": "cfg3_4k", "width": W, "height": H, "max_steps": cfg.max_steps, "disk": [r_in, r_out],
+        "shift": [1, 4, 1.0], "emission": emission, "ramp_entries": 256,
+        "n": args.n, "warmup": args.warmup, "settling_alternations_not_counted": settling, "alternations": blocks,
+        "shift_ms_median": float(np.median(sm)), "emission_ms_median": float(np.median(em)),
+        "emission_over_shift": float(np.median(em) / np.median(sm)),
+        "emission_over_shift_min": float(min(b["emission_over_shift"] for b in blocks)),
+        "emission_over_shift_max": float(max(b["emission_over_shift"] for b in blocks)),
+        "shift_alternation_spread": float((sm.max() - sm.min()) / np.median(sm)),
+        "hit_pixel_share": float(hit.any(dim=-1).float().mean()),
+        "q_max": float(qv.max()),
+        "timing": "geo_time_next_render event pairs on each kernel dispatch; blocks of n shaded renders and n emission "
+                  "renders alternate in one process, each kind on its own context",
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    doc = []  # every run is kept, as --shift's are
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            doc = json.load(f)
+    doc.append(res)
     with open(args.out, "w") as f:
         f.write(json.dumps(doc, indent=1) + "\n")
 

@@ -8,6 +8,7 @@ the present step of the absent wgpu_renderer loop.
         [--frames 60 --orbit 3.2] [--mipmaps] [--fan]
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
+        [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -16,7 +17,12 @@ images) instead of the reference's scene; --cpu renders it with the CPU path
 shades the disk by its Doppler and redshift factor g (geo_set_disk_shift:
 matter orbiting about SPIN * normal, colours times GAIN * g**EXP).  --ss
 draws the disk frame 2 x 2 supersampled (GEO_FLAG_SS4: four rays per pixel,
-resolved in the kernel), on the GPU or with --cpu.
+resolved in the kernel), on the GPU or with --cpu.  --disk-emission T_REF T_LO
+T_HI EXPOSURE colours the disk by its observed blackbody temperature
+(geo_set_disk_emission: T = T_REF tau(r) with the --disk-profile, shifted by g
+for matter orbiting about --disk-spin * normal, a 256-entry
+scenes.blackbody_ramp from T_LO to T_HI, brightness EXPOSURE (T_obs/T_REF)**4);
+it takes the place of --disk-shift and works with --cpu and --ss.
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -41,9 +47,15 @@ def disk_frame(args):
 
     import schwarzschild_raytracer_wgpu_amd as g
     from schwarzschild_raytracer_wgpu_amd import _lib, imageio
-    from schwarzschild_raytracer_wgpu_amd.scenes import make_disk_texture, make_sky
+    from schwarzschild_raytracer_wgpu_amd.scenes import blackbody_ramp, make_disk_texture, make_sky
 
     w, h = args.width, args.height
+    emission = ramp = None
+    if args.disk_emission:
+        t_ref, t_lo, t_hi, exposure = args.disk_emission
+        profile = _lib.GEO_DISK_PROFILE_POWER if args.disk_profile == "power" else _lib.GEO_DISK_PROFILE_THIN
+        emission = _lib.GeoDiskEmission(args.disk_spin, profile, t_ref, t_lo, t_hi, exposure)
+        ramp = blackbody_ramp(256, t_lo, t_hi)
     obs = g.Observer(1.0, args.fov, w, h)
     obs.set_position(*args.pos)
     obs.set_camera(*args.camera)
@@ -59,19 +71,27 @@ def disk_frame(args):
         sky = np.ascontiguousarray(sky)
         rgba = np.zeros((h, w, 4), np.uint8)
         vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-        shift = None
-        if args.disk_shift:
-            shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
-        lib.geo_render_cpu_disk_shift.restype = ctypes.c_int
-        lib.geo_render_cpu_disk_shift.argtypes = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int,
-                                                  vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]
-        rc = lib.geo_render_cpu_disk_shift(ctypes.addressof(frame), ctypes.addressof(scene), sky.ctypes.data,
-                                           sky.shape[1], sky.shape[0], None, 0, w, h, 0, h, 1, 0, rgba.ctypes.data,
-                                           None, None, None, None, ctypes.addressof(disk), tex.ctypes.data,
-                                           tex.shape[1], tex.shape[0], None,
-                                           ctypes.addressof(shift) if shift else None, None)
+        common = [ctypes.addressof(frame), ctypes.addressof(scene), sky.ctypes.data, sky.shape[1], sky.shape[0], None, 0,
+                  w, h, 0, h, 1, 0, rgba.ctypes.data, None, None, None, None, ctypes.addressof(disk), tex.ctypes.data,
+                  tex.shape[1], tex.shape[0], None]
+        base = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, u32,
+                u32, vp]
+        if emission is not None:
+            name = "geo_render_cpu_disk_emission"
+            lib.geo_render_cpu_disk_emission.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_emission.argtypes = base + [vp, vp, u32, vp, vp]
+            rc = lib.geo_render_cpu_disk_emission(*common, ctypes.addressof(emission), ramp.ctypes.data, ramp.shape[0],
+                                                  None, None)
+        else:
+            name = "geo_render_cpu_disk_shift"
+            shift = None
+            if args.disk_shift:
+                shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
+            lib.geo_render_cpu_disk_shift.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_shift.argtypes = base + [vp, vp]
+            rc = lib.geo_render_cpu_disk_shift(*common, ctypes.addressof(shift) if shift else None, None)
         if rc != 0:
-            raise SystemExit(f"geo_render_cpu_disk_shift: {rc}")
+            raise SystemExit(f"{name}: {rc}")
     else:
         import torch
 
@@ -80,6 +100,9 @@ def disk_frame(args):
         ctx.set_disk(tex, r_in, r_out, normal=args.disk_normal)
         if args.disk_shift:
             ctx.set_disk_shift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
+        if emission is not None:
+            ctx.set_disk_emission(ramp, emission.t_ref, emission.t_lo, emission.t_hi, emission.profile,
+                                  emission.exposure, emission.spin)
         rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
         ctx.render_rows(frame, scene, w, h, 0, h, rgba)
     if args.out.endswith(".ppm"):
@@ -114,7 +137,11 @@ def main():
     p.add_argument("--disk-normal", type=float, nargs=3, default=(0.0, 0.0, 1.0))
     p.add_argument("--disk-shift", type=float, nargs=3, metavar=("SPIN", "EXP", "GAIN"),
                    help="with --disk: Doppler and redshift shading (geo_set_disk_shift)")
-    p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (geo_render_cpu_disk_shift)")
+    p.add_argument("--disk-emission", type=float, nargs=4, metavar=("T_REF", "T_LO", "T_HI", "EXPOSURE"),
+                   help="with --disk: blackbody emission (geo_set_disk_emission), in place of --disk-shift")
+    p.add_argument("--disk-profile", choices=("power", "thin"), default="thin", help="with --disk-emission")
+    p.add_argument("--disk-spin", type=int, choices=(1, -1), default=1, help="with --disk-emission")
+    p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
     p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
     p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
