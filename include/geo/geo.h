@@ -60,13 +60,16 @@ extern "C" {
                                    announced by GEO_HAS_SS4: GEO_FLAG_SS4;
                                    announced by GEO_HAS_SS4_BATCH: geo_render_ss_batch;
                                    announced by GEO_HAS_DISK_EMISSION: geo_disk_emission,
-                                   geo_set_disk_emission, geo_disk_emission_next_render) */
+                                   geo_set_disk_emission, geo_disk_emission_next_render;
+                                   announced by GEO_HAS_DISK_EMISSION_BATCH:
+                                   geo_render_emission_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
 #define GEO_HAS_SS4 1
 #define GEO_HAS_SS4_BATCH 1
 #define GEO_HAS_DISK_EMISSION 1
+#define GEO_HAS_DISK_EMISSION_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -369,8 +372,8 @@ typedef struct geo_disk_emission {
  * too), and GEO_FLAG_SS4 on those three, colour only.  geo_render_disk_batch,
  * and geo_render_ss_batch for a GEO_FLAG_DISK scene, return GEO_EINVAL while an
  * emission is set, launch nothing and write nothing: a batched disk frame
- * would come out without its emission.  Batched emission frames are the
- * stated follow-up. */
+ * would come out without its emission.  Batched emission frames go through
+ * geo_render_emission_batch (GEO_HAS_DISK_EMISSION_BATCH). */
 int geo_set_disk_emission(geo_ctx* ctx, const geo_disk_emission* emission, const uint8_t* ramp_rgba8, uint32_t n);
 /* The next render of this context writes its hits' q = T_obs / t_ref to out_q
  * (device, nrows*width*3 floats, laid out as the render's rows): element k of
@@ -497,8 +500,8 @@ int geo_render_band_set_batch(geo_ctx* ctx, const geo_frame* frames, const geo_s
  * geo_disk_hits_next_render, geo_disk_shift_next_render or
  * geo_disk_emission_next_render is consumed and the call returns GEO_EINVAL.
  * While geo_set_disk_emission is set the call returns GEO_EINVAL (batched
- * emission frames are a follow-up; the one-frame entry points draw them).  A
- * refused call launches nothing and writes nothing.
+ * emission frames go through geo_render_emission_batch; the one-frame entry
+ * points draw them too).  A refused call launches nothing and writes nothing.
  * The executed steps of all frames go to steps_total or, with
  * GEO_FLAG_DEFER_STEPS, to the context's accumulator; geo_time_next_render and
  * the dispatch order work as for the other batches (frame 0 records the tile
@@ -544,6 +547,36 @@ int geo_render_ss_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* 
                         uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                         uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                         unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for the blackbody disk (GEO_HAS_DISK_EMISSION_BATCH):
+ * nframes (1 .. GEO_MAX_BATCH_FRAMES) frames of the context's thin disk with
+ * geo_set_disk_emission set, in ONE launch, scenes[f] for frames[f], the
+ * band-set layout and the out_frame_stride rules of the other batches.  Frame
+ * f's bytes are those of geo_render_band_set with frames[f], scenes[f] and the
+ * same context state, bit for bit (and so geo_render_cpu_disk_emission's).
+ * Every scene carries GEO_FLAG_DISK and GEO_MODE_DIRECT; GEO_FLAG_SS4 on all of
+ * them or on none (width, height, rows and bands are then in output pixels, as
+ * for geo_render_ss_batch, with its size limits); GEO_FLAG_DEFER_STEPS is
+ * allowed and nothing else.  The scenes may differ in r_obs only and share the
+ * integration kind.  geo_render_disk_batch's disk rules and the emission's
+ * r_in > 1.5 rs rule hold for every frame's scene, else GEO_EINVAL.
+ * GEO_ESTATE when no sky, no disk or no emission is set.  While
+ * geo_set_disk_shift is set too, the emission takes its place (its own spin),
+ * as in the one-frame render.  Colour only: a buffer armed by
+ * geo_disk_hits_next_render, geo_disk_shift_next_render or
+ * geo_disk_emission_next_render is consumed and the call returns GEO_EINVAL.
+ * A refused call launches nothing and writes nothing; ctx, frames, scenes or
+ * out_rgba8 NULL and nframes out of range are refused before any device work.
+ * steps_total and the deferred accumulator, geo_time_next_render,
+ * geo_set_dispatch and geo_set_tile_order work as for the other batches (frame
+ * 0 records the tile costs; under GEO_FLAG_SS4 the grid is the sample frame's).
+ * geo_render_disk_batch, geo_render_ss_batch and geo_render_band_set_frames /
+ * _batch keep refusing what they refuse.  One scene for every frame: pass
+ * copies.  Asynchronous on `stream`. */
+int geo_render_emission_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                              uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                              uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                              unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

@@ -690,6 +690,10 @@ struct RenderCall {
     // geo_render_ss_batch (GEO_FLAG_SS4 scenes, any nframes, through the
     // batched SS kernels); the other entry points draw an SS frame alone
     bool ss_batch = false;
+    // geo_render_emission_batch (GEO_FLAG_DISK scenes with the emission set,
+    // with GEO_FLAG_SS4 or without, any nframes, through the batched emission
+    // kernels); the other entry points draw an emission frame alone
+    bool emit_batch = false;
     uint32_t width, height, row0, nrows, band_rows, band_stride;
     uint8_t* out_rgba8;
     uint8_t* out_mask = nullptr;  // (a batch draws colour only)
@@ -734,7 +738,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // and DEFER_STEPS at most, and a sample frame of twice the size that the
     // entry points take
     w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
-    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && rc.nframes != 1) ||
+    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && !rc.emit_batch && rc.nframes != 1) ||
                  scene->mode != GEO_MODE_DIRECT ||
                  (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
                  rc.out_uv || rc.out_steps || w.out_hits || w.out_g || w.out_q || rc.width > (1u << 19) ||
@@ -751,8 +755,13 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // geo_render_disk_batch draws disk scenes only, and colour only: an armed
     // per-pixel buffer (consumed by render_impl) refuses the call
     if (rc.disk_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
-    // geo_set_disk_emission: the one-frame entry points only (a batched disk
-    // frame would come out without its emission: refused, nothing launched)
+    // geo_render_emission_batch likewise (all of its scenes with GEO_FLAG_SS4
+    // or none: fill_frames' rule that a batch's flags agree); without the
+    // emission set it has nothing to draw (GEO_ESTATE, after the disk's below)
+    if (rc.emit_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
+    // geo_set_disk_emission: the one-frame entry points and geo_render_emission_batch
+    // (through the older batched calls a disk frame would come out without
+    // its emission: refused, nothing launched)
     w.emit = w.disk && c->emit_set;
     if (w.emit && (rc.disk_batch || rc.ss_batch)) return GEO_EINVAL;
     w.ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
@@ -779,6 +788,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
         return GEO_EINVAL;
     if (w.disk) {
         if (!c->disk_set) return GEO_ESTATE;
+        if (rc.emit_batch && !c->emit_set) return GEO_ESTATE;
         if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < c->disk.r_in)) ||
             !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
             return GEO_EINVAL;
@@ -1073,9 +1083,13 @@ static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderW
 
 // A batch's DiskBatchArgs: every frame's constants by the one-frame launch's
 // own functions (geo_render_disk_batch, and geo_render_ss_batch's disk frames,
-// whose w.fk holds the sample frame's camera).
-static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderWork& w, DiskBatchArgs& db) {
+// whose w.fk holds the sample frame's camera).  eb (geo_render_emission_batch):
+// the emission's batch-uniform argument, filled too; the frames' sb and ih are
+// then the emission's.
+static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderWork& w, DiskBatchArgs& db,
+                           DiskEmitBatchArgs* eb = nullptr) {
     std::memset(&db, 0, sizeof(db));
+    if (eb) std::memset(eb, 0, sizeof(*eb));
     for (uint32_t i = 0; i < rc.nframes; ++i) {
         const geo_scene& si = rc.scene_per_frame ? rc.scene[i] : *rc.scene;
         DiskFrameK& f = db.f[i];
@@ -1096,7 +1110,25 @@ static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderW
         }
         f.u_lo = dk.u_lo;
         f.u_hi = dk.u_hi;
-        if (c->shift_set) {
+        if (eb) {
+            // the emission takes the shift's place (geo_set_disk_shift's state
+            // is not read): sb and ih with the emission's spin, by the
+            // one-frame launch's function (emit_args); the rest of it is the
+            // same for every frame
+            const geo::DiskEmission ek =
+                geo::disk_emission_consts(rc.frames[i].central_to_uv, si.rs, si.r_obs, c->emit.spin, c->emit.profile,
+                                          c->emit.t_ref, c->emit.t_lo, c->emit.t_hi, c->emit.exposure, c->emit_n);
+            f.sb = ek.s.sb;
+            f.ih = ek.s.ih;
+            eb->inv_fmax = ek.inv_fmax;
+            eb->ka = ek.ka;
+            eb->kb = ek.kb;
+            eb->n1 = ek.n1;
+            eb->exposure = ek.exposure;
+            eb->profile = ek.profile;
+            eb->n2 = ek.n2;
+            eb->ramp = c->emit_ramp;
+        } else if (c->shift_set) {
             const geo::DiskShift sk = geo::disk_shift_consts(rc.frames[i].central_to_uv, si.rs, si.r_obs,
                                                              c->shift.spin, c->shift.exponent, c->shift.gain);
             f.sb = sk.sb;
@@ -1163,8 +1195,36 @@ static int launch_ss_frames(const geo_ctx* c, const RenderCall& rc, const Render
     });
 }
 
+// Stage 5, geo_render_emission_batch: launch_disk_batch's and launch_ss_frames'
+// geometry (one wave per workgroup on the 1-D wave-block grid, the frames in
+// grid.z) with the emission kernels; with GEO_FLAG_SS4, w.fk holds each
+// frame's camera at 2W x 2H and the grid is the sample frame's.
+static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(DiskEmitBatchArgs) + sizeof(SsBatchOut) <= 4096,
+              "kernel arguments fit 4 KiB");
+static int launch_emit_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    DiskBatchArgs db;
+    DiskEmitBatchArgs eb;
+    if (const int st = fill_disk_batch(c, rc, w, db, &eb)) return st;
+    SsBatchOut x;
+    x.out_width = rc.width;
+    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
+                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+            const dim3 grid(wave_block_count(la.launch_tiles), 1, rc.nframes), block(64);
+            if (w.ss)
+                hipExtLaunchKernelGGL(geo_render_ss_emit_batch_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0, la,
+                                      db, eb, x);
+            else
+                hipExtLaunchKernelGGL(geo_render_disk_emit_batch_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0,
+                                      la, db, eb);
+        });
+    });
+}
+
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    if (rc.emit_batch) return launch_emit_frames(c, rc, w);
     if (w.ss) return rc.ss_batch ? launch_ss_frames(c, rc, w) : launch_ss_frame(c, rc, w);
     if (w.disk) return rc.disk_batch ? launch_disk_frames(c, rc, w) : launch_disk_frame(c, rc, w);
     if (rc.scene->mode == GEO_MODE_FAN) return launch_fan(c, rc, w);
@@ -1590,6 +1650,23 @@ int geo_render_ss_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* sc
     rc.scene_per_frame = true;
     rc.allow_disk = true;
     rc.ss_batch = true;
+    return render_impl(c, rc);
+}
+
+int geo_render_emission_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                              uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                              uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                              unsigned long long* steps_total, void* stream) {
+    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
+        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
+        return invalid_call(c);
+    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
+                                out_rgba8, steps_total, stream);
+    rc.nframes = nframes;
+    rc.out_frame_stride = out_frame_stride;
+    rc.scene_per_frame = true;
+    rc.allow_disk = true;
+    rc.emit_batch = true;
     return render_impl(c, rc);
 }
 

@@ -1371,6 +1371,223 @@ __global__ __launch_bounds__(64) void geo_render_ss_batch_kernel(const RenderArg
     }
 }
 
+// ---- geo_render_emission_batch: up to kMaxBatchFrames emission frames in one launch --
+// geo_render_disk_batch_kernel's shaded body and geo_render_ss_batch_kernel's
+// disk body with geo::disk_shade_emit as the hit arm (null per-pixel outputs:
+// a batch draws colour only).  Kernels of their own, not a further template
+// parameter or VAR of those two: their code, argument segments and resource
+// records stay as they were.  DiskBatchArgs is reused unchanged: of a
+// geo::DiskEmission only sb and ih change with the frame (its r_obs and
+// det M2), and DiskFrameK carries them, filled by geo::disk_emission_consts
+// with the emission's spin; the batch-uniform rest and the ramp ride in one
+// further argument.  Everything read here per frame or per batch is
+// wave-uniform (scalar loads); the ramp's two entries are loaded inside the hit
+// arm only, as in geo_render_disk_emit_kernel.
+struct DiskEmitBatchArgs {
+    float inv_fmax, ka, kb, n1, exposure;  // geo::DiskEmission, batch-uniform
+    uint32_t profile, n2;
+    const uint32_t* ramp;  // n2 + 2 RGBA8 entries
+};
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                        const DiskEmitBatchArgs eb) {
+    const uint32_t z = blockIdx.z;
+    const DiskFrameK& f = db.f[z];
+    const size_t obase = (size_t)z * a.out_frame_px;
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    uint32_t steps = 0;
+    if (px < a.width && ly < a.nrows && py < a.height) {
+        float c2x, c2y, c2z, g_obs;
+        geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
+        geo::DiskConsts dk;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            dk.N[i] = f.N[i];
+            dk.ex[i] = f.ex[i];
+            dk.ey[i] = f.ey[i];
+        }
+        dk.r_in = db.r_in;
+        dk.r_out = db.r_out;
+        dk.inv_dr = db.inv_dr;
+        dk.u_lo = f.u_lo;
+        dk.u_hi = f.u_hi;
+        dk.inv_step = db.inv_step;
+        const geo::PixelConsts& k = f.k;
+        geo::DiskRay dr;
+        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const size_t o = obase + (size_t)ly * a.width + px;
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
+                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
+                                  db.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
+        };
+        const auto rfetch = [ramp = eb.ramp](uint32_t i) { return ramp[i]; };
+        // frame z's geo::DiskEmission (its gain and exponent are not read)
+        geo::DiskEmission ek;
+        ek.s.sb = f.sb;
+        ek.s.ih = f.ih;
+        ek.s.gain = 1.0f;
+        ek.s.exponent = 0u;
+        ek.inv_fmax = eb.inv_fmax;
+        ek.ka = eb.ka;
+        ek.kb = eb.kb;
+        ek.n1 = eb.n1;
+        ek.exposure = eb.exposure;
+        ek.profile = eb.profile;
+        ek.n2 = eb.n2;
+        geo::DiskShiftRay sr;
+        geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
+        a.out_rgba[o] = geo::disk_shade_emit(dk, k, dr, ek, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
+                                             nullptr);
+    }
+    // (every lane of the wave is active again here, as in geo_render_kernel)
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
+// The same with GEO_FLAG_SS4: a lane per sample of the 2W x 2H frame, resolved
+// across the wave's lanes (geo_render_ss_batch_kernel's sample grid, band
+// mapping on output rows and quad parity, which see).
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_ss_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                      const DiskEmitBatchArgs eb,
+                                                                      const SsBatchOut x) {
+    const uint32_t z = blockIdx.z;
+    const DiskFrameK& f = db.f[z];
+    const size_t obase = (size_t)z * a.out_frame_px;
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    // the only early exit, and a wave-uniform one: ss_resolve below needs every lane
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // the sample's colour, kept in a register
+    if (in_frame) {
+        float c2x, c2y, c2z, g_obs;
+        geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
+        geo::DiskConsts dk;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            dk.N[i] = f.N[i];
+            dk.ex[i] = f.ex[i];
+            dk.ey[i] = f.ey[i];
+        }
+        dk.r_in = db.r_in;
+        dk.r_out = db.r_out;
+        dk.inv_dr = db.inv_dr;
+        dk.u_lo = f.u_lo;
+        dk.u_hi = f.u_hi;
+        dk.inv_step = db.inv_step;
+        const geo::PixelConsts& k = f.k;
+        geo::DiskRay dr;
+        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+        float Uk[geo::kDiskMaxCrossings];
+        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+        const float lam = geo::kPi2 - ang;
+        const bool bh = lam < geo::kBlackHoleLambda;
+        float U = 0.0f, V = 0.0f;
+        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
+                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
+                                  db.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
+        };
+        const auto rfetch = [ramp = eb.ramp](uint32_t i) { return ramp[i]; };
+        // frame z's geo::DiskEmission (its gain and exponent are not read)
+        geo::DiskEmission ek;
+        ek.s.sb = f.sb;
+        ek.s.ih = f.ih;
+        ek.s.gain = 1.0f;
+        ek.s.exponent = 0u;
+        ek.inv_fmax = eb.inv_fmax;
+        ek.ka = eb.ka;
+        ek.kb = eb.kb;
+        ek.n1 = eb.n1;
+        ek.exposure = eb.exposure;
+        ek.profile = eb.profile;
+        ek.n2 = eb.n2;
+        geo::DiskShiftRay sr;
+        geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
+        colour = geo::disk_shade_emit(dk, k, dr, ek, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
+                                      nullptr);
+    }
+    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
+    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
+    // of the frame resolves four zeros and is not stored.
+    const uint32_t resolved = ss_resolve(colour);
+    if (in_frame && (lane & 0x11u) == 0u)
+        a.out_rgba[obase + (size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
+        const uint32_t wmax = wave_max_u32(steps);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
 // bits of the cost, 256 classes), dispatched from the highest class down;
@@ -1805,6 +2022,12 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_ss_emit_kernel<geo::kCurvedOut>;
     (void)geo_render_ss_emit_kernel<geo::kCurvedIn>;
     (void)geo_render_ss_emit_kernel<geo::kFlat>;
+    (void)geo_render_disk_emit_batch_kernel<geo::kCurvedOut>;
+    (void)geo_render_disk_emit_batch_kernel<geo::kCurvedIn>;
+    (void)geo_render_disk_emit_batch_kernel<geo::kFlat>;
+    (void)geo_render_ss_emit_batch_kernel<geo::kCurvedOut>;
+    (void)geo_render_ss_emit_batch_kernel<geo::kCurvedIn>;
+    (void)geo_render_ss_emit_batch_kernel<geo::kFlat>;
 }
 
 }  // namespace

@@ -216,7 +216,8 @@ class ShardedFrame:
 
     def __init__(self, ctx, frame, scene, width: int, height: int, band_rows: int, rank: int, world: int, device,
                  dist=None, host_gather: bool = False, frames_per_gather: int = 1, render_streams: int = 1,
-                 present_rgb: bool = True, lead: int = 1, batch_launch: bool = False, peer_bands: int = 1):
+                 present_rgb: bool = True, lead: int = 1, batch_launch: bool = False, peer_bands: int = 1,
+                 emission_batch: bool = False):
         """host_gather: stage through host memory (gloo backend; rehearsals only).
         present_rgb: peers send RGB24 (geo_pack_rgb after each render; 25 %
         fewer bytes on the links) when the width is a multiple of 4.
@@ -228,7 +229,11 @@ class ShardedFrame:
         (geo_render_band_set_frames) when it is complete, on render stream
         (batch buffer % S): a launch's fixed cost (dispatch, ramp, drain) is
         paid once per batch instead of per frame; a peer's share at N = 8
-        draws 10-12 % faster per frame.  K <= GEO_MAX_BATCH_FRAMES."""
+        draws 10-12 % faster per frame.  K <= GEO_MAX_BATCH_FRAMES.
+        emission_batch: with batch_launch, a GEO_FLAG_DISK scene of a context
+        with set_disk_emission on goes to geo_render_emission_batch (with
+        GEO_FLAG_SS4 or without); without it such a scene is refused, as the
+        older batched entry points refuse it."""
         import torch
 
         from ._lib import lib
@@ -247,6 +252,7 @@ class ShardedFrame:
         from ._lib import GEO_MAX_BATCH_FRAMES
 
         self.batch = bool(batch_launch) and self.K > 1
+        self.emission_batch = bool(emission_batch)
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
         if self.batch:
@@ -335,22 +341,30 @@ class ShardedFrame:
         k = (i // self.K) % 2 % self.S if self.batch else i % self.S
         return self.stream0 if k == 0 else self.extra[k - 1]
 
-    def _refuse_emission_batch(self, scene) -> None:
-        """The batched entry points draw no emission frames (geo_set_disk_emission,
-        geo.h): a GEO_FLAG_DISK scene of a context with the emission set is
-        refused here, by name, instead of by the launch's GEO_EINVAL."""
+    def _emission_scene(self, scene) -> bool:
+        """A GEO_FLAG_DISK scene of a context with the emission set."""
         from ._lib import GEO_FLAG_DISK
 
-        if scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_emission_set", False):
-            raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on (batched emission frames "
-                             "are not built yet): use batch_launch=False, or clear_disk_emission()")
+        return bool(scene is not None and scene.flags & GEO_FLAG_DISK
+                    and getattr(self.ctx, "disk_emission_set", False))
+
+    def _refuse_emission_batch(self, scene) -> None:
+        """The older batched entry points draw no emission frames
+        (geo_set_disk_emission, geo.h): without emission_batch a GEO_FLAG_DISK
+        scene of a context with the emission set is refused here, by name,
+        instead of by the launch's GEO_EINVAL."""
+        if not self.emission_batch and self._emission_scene(scene):
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on through the older batched "
+                             "entry points: pass emission_batch=True (geo_render_emission_batch), or use "
+                             "batch_launch=False, or clear_disk_emission()")
 
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
         """The frames of batch buffer b (slots first .. first + len(frames) - 1)
         in one launch (geo_render_band_set_batch, geo_render_ss_batch for
         GEO_FLAG_SS4 scenes, or geo_render_disk_batch for GEO_FLAG_DISK
-        scenes without it), on `stream` (a handle;
+        scenes without it; with emission_batch, geo_render_emission_batch for
+        a disk scene while the emission is set), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
         from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4, GeoFrame, GeoScene, check
@@ -373,7 +387,9 @@ class ShardedFrame:
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
         self._refuse_emission_batch(scenes[0])
-        if scenes[0].flags & GEO_FLAG_SS4:
+        if self.emission_batch and self._emission_scene(scenes[0]):
+            name = "geo_render_emission_batch"  # (with GEO_FLAG_SS4 or without)
+        elif scenes[0].flags & GEO_FLAG_SS4:
             name = "geo_render_ss_batch"
         elif scenes[0].flags & GEO_FLAG_DISK:
             name = "geo_render_disk_batch"

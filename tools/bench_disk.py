@@ -41,6 +41,23 @@ passes: by a pair of stream events around the launches (what a pipeline waits
 for: dispatch gaps included), and by geo_time_next_render pairs on the kernel
 dispatches alone (the K one-frame times added up).  Medians of --n samples;
 the ratios are per frame, batch over one-frame launches.
+
+--batch K --emission measures the batched emission launch
+(geo_render_emission_batch) on the same layout, with --emission's state (THIN
+profile, a 256-entry ramp): one launch of K emission frames, K one-frame
+geo_render_band_set launches of the same frames back to back (the yardstick),
+and one shaded geo_render_disk_batch launch of K frames alternate, each on its
+own context.  A session builds and warms the contexts up, then takes
+--alternations (5) times --n (30) samples of each side, by stream events around
+the launches and then by the dispatches' own event pairs, each after --settle
+(4) alternations of the same form that are reported apart; each side's median
+of the n is the alternation's figure.  Per session and timing it reports the
+medians of those per frame, batch over one-frame launches, the one-frame
+side's spread ((max - min) / median of its alternation medians), the margin
+1 - 2 x that spread the batch has to beat, and the emission batch over the
+shaded batch.  --sessions (2) sessions go into one JSON object.
+
+  python tools/bench_disk.py --batch 8 --emission [--out profiles/disk_emission_batch_bench_cfg3.json]
 """
 from __future__ import annotations
 
@@ -65,15 +82,23 @@ def main():
                    help="with --emission: alternations run first in the timed form, reported apart and not counted")
     p.add_argument("--batch", type=int, default=0, metavar="K",
                    help="measure one launch of K disk frames against K one-frame launches (a peer's share at N = 8)")
+    p.add_argument("--sessions", type=int, default=2,
+                   help="with --batch K --emission: sessions (contexts built, warmed up and timed anew)")
+    p.add_argument("--shaded-first", action="store_true",
+                   help="with --batch K --emission: the shaded batch is each sample's first launch, the emission "
+                        "batch its last (default: the other way round)")
     p.add_argument("--out")
     args = p.parse_args()
     if not args.out:
-        name = "disk_batch_bench_cfg3.json" if args.batch else (
+        name = "disk_emission_batch_bench_cfg3.json" if args.batch and args.emission else (
+            "disk_batch_bench_cfg3.json") if args.batch else (
             "disk_emission_bench_cfg3.json" if args.emission else (
                 "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json"))
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.batch and args.emission:
+        return emission_batch_main(args)
     if args.batch:
         return batch_main(args)
     if args.emission:
@@ -375,6 +400,160 @@ def batch_main(args):
     for how, ms in (("stream_events", stream_ms), ("dispatch_events", disp_ms)):
         for tag in ("disk", "shift"):
             res[how][tag + "_batch_over_single"] = float(np.median(ms[tag + "_batch"]) / np.median(ms[tag + "_single"]))
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+def emission_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission):
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.dist import BandLayout
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent, hipEventDefault
+
+    K = args.batch
+    W, H = cfg.width, cfg.height
+    L = BandLayout(H, 8, 8, 1)  # a peer's share at N = 8
+    band = (L.band_height(), L.row0(), L.cycle_rows, L.nbands())
+    packed = L.packed_rows() * W * 4
+    dev = torch.device("cuda:0")
+    out = torch.empty(K * packed, dtype=torch.uint8, device=dev)
+    sh = torch.cuda.current_stream().cuda_stream
+    frames = (_lib.GeoFrame * K)(*([frame] * K))
+    scenes = (_lib.GeoScene * K)(*([scene] * K))
+    lib = _lib.lib
+
+    def make_ctx(emit):
+        c = g.Context(0)
+        c.set_sky(sky)
+        c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+        if emit:
+            c.set_disk_emission(ramp, **emission)
+        else:
+            c.set_disk_shift(1, 4, 1.0)
+        return c
+
+    def run_batch(name):
+        fn = getattr(lib, name)
+
+        def run(c, pairs=None):
+            if pairs is not None:
+                c.time_next_render(*pairs[0])
+            _lib.check(name, fn(c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
+        return run
+
+    def run_singles(c, pairs=None):
+        for k in range(K):
+            if pairs is not None:
+                c.time_next_render(*pairs[k])
+            _lib.check("geo_render_band_set", lib.geo_render_band_set(
+                c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None,
+                None, None, sh))
+
+    # (each side on its own context: the learned dispatch order is kept per context)
+    sides = [("emission_batch", make_ctx(True), run_batch("geo_render_emission_batch"), 1),
+             ("emission_single", make_ctx(True), run_singles, K),
+             ("shift_batch", make_ctx(False), run_batch("geo_render_disk_batch"), 1)]
+    if args.shaded_first:
+        # a sample's first launch starts on an idle stream and pays its wake-up inside the stream events' pair; the
+        # launches behind it are queued while it runs: which batch is first decides a few microseconds between them
+        sides.reverse()
+    for _ in range(args.warmup):
+        for _, c, run, _ in sides:
+            run(c)
+    torch.cuda.synchronize()
+    res = {"layout": {"world": 8, "rank": 1, "band_rows": band[0], "row0": band[1], "row_stride": band[2],
+                      "nbands": band[3], "rows": L.rows_mine()}}
+    for how in ("stream_events", "dispatch_events"):
+        # --settle alternations are run first in the timed form and kept apart, as --emission does: without them the
+        # second alternation of a session's first timing ran 10-16 % slower for all three sides together, in two runs
+        # out of two (profiles/disk_emission_batch_bench_cfg3_unsettled.json)
+        med = {name: [] for name, *_ in sides}
+        settling = {name: [] for name, *_ in sides}
+        for alt in range(args.settle + args.alternations):
+            ev = {name: [] for name, *_ in sides}
+            for _ in range(args.n):
+                for name, c, run, m in sides:
+                    if how == "stream_events":
+                        a, b = HipEvent(hipEventDefault), HipEvent(hipEventDefault)
+                        a.record(sh)
+                        run(c)
+                        b.record(sh)
+                        ev[name].append([(a, b)])
+                    else:
+                        pairs = [(HipEvent(), HipEvent()) for _ in range(m)]
+                        run(c, pairs)
+                        ev[name].append(pairs)
+                torch.cuda.synchronize()  # the next sample's launches queue behind nothing
+            for name, v in ev.items():
+                (settling if alt < args.settle else med)[name].append(
+                    float(np.median([sum(a.elapsed_time(b) for a, b in pairs) for pairs in v]) / K))
+        b_m, s_m = float(np.median(med["emission_batch"])), float(np.median(med["emission_single"]))
+        sb_m = float(np.median(med["shift_batch"]))
+        spread = (max(med["emission_single"]) - min(med["emission_single"])) / s_m
+        res[how] = {
+            "settling_alternations_not_counted": settling,
+            "emission_batch_ms_per_frame_medians": med["emission_batch"],
+            "emission_single_ms_per_frame_medians": med["emission_single"],
+            "shift_batch_ms_per_frame_medians": med["shift_batch"],
+            "emission_batch_ms_per_frame": b_m, "emission_single_ms_per_frame": s_m, "shift_batch_ms_per_frame": sb_m,
+            "batch_over_single": b_m / s_m, "single_spread": spread,
+            "batch_spread": (max(med["emission_batch"]) - min(med["emission_batch"])) / b_m,
+            # the batch is held to a saving of more than twice the one-frame side's own spread
+            "margin": 1.0 - 2.0 * spread, "faster_by_more_than_margin": bool(b_m < s_m * (1.0 - 2.0 * spread)),
+            "emission_batch_over_shift_batch": b_m / sb_m,
+        }
+    for _, c, *_ in sides:
+        c.close()
+    return res
+
+
+def emission_batch_main(args):
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, blackbody_ramp, make_disk_texture, make_sky
+
+    K = args.batch
+    if not 1 <= K <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise SystemExit(f"--batch: 1 .. {_lib.GEO_MAX_BATCH_FRAMES}")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg = CONFIGS["cfg3_4k"]
+    obs = g.Observer(cfg.rs, cfg.fov, cfg.width, cfg.height)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg.step, cfg.max_steps,
+                         flags=_lib.GEO_FLAG_DISK)
+    emission = dict(t_ref=9000.0, t_lo=1500.0, t_hi=30000.0, profile=_lib.GEO_DISK_PROFILE_THIN, exposure=1.0, spin=1)
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    ramp = blackbody_ramp(256, emission["t_lo"], emission["t_hi"])
+    res = {
+        "config": "cfg3_4k", "width": cfg.width, "height": cfg.height, "max_steps": cfg.max_steps,
+        "disk": [1.6 * cfg.rs, 2.2 * cfg.rs], "emission": emission, "ramp_entries": 256, "shift": [1, 4, 1.0],
+        "frames_per_batch": K, "n": args.n, "alternations": args.alternations, "settle": args.settle,
+        "order_in_a_sample": ["shift_batch", "emission_single", "emission_batch"] if args.shaded_first else [
+            "emission_batch", "emission_single", "shift_batch"],
+        "warmup": args.warmup,
+        "timing": "stream_events: a pair of events on the stream around one launch of K frames, or around K one-frame "
+                  "launches back to back; dispatch_events: geo_time_next_render pairs on the kernel dispatches, the K "
+                  "one-frame times added; emission_batch (geo_render_emission_batch), emission_single (K "
+                  "geo_render_band_set launches, the yardstick) and shift_batch (the shaded geo_render_disk_batch on "
+                  "the same layout) alternate, each on its own context; per alternation the median of n, after settle "
+                  "alternations of each timing that are kept apart; spread = "
+                  "(max - min) / median of a side's alternation medians; margin = 1 - 2 x the one-frame side's spread",
+        "sessions": [emission_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission)
+                     for _ in range(args.sessions)],
+    }
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
