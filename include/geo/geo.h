@@ -62,7 +62,8 @@ extern "C" {
                                    announced by GEO_HAS_DISK_EMISSION: geo_disk_emission,
                                    geo_set_disk_emission, geo_disk_emission_next_render;
                                    announced by GEO_HAS_DISK_EMISSION_BATCH:
-                                   geo_render_emission_batch) */
+                                   geo_render_emission_batch;
+                                   announced by GEO_HAS_DISK_RING_F64: geo_set_disk_ring_f64) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -70,6 +71,7 @@ extern "C" {
 #define GEO_HAS_SS4_BATCH 1
 #define GEO_HAS_DISK_EMISSION 1
 #define GEO_HAS_DISK_EMISSION_BATCH 1
+#define GEO_HAS_DISK_RING_F64 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -151,9 +153,12 @@ typedef enum geo_status {
                                    (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
                                    A ray the reference ends before its loop (its pre-filters
                                    and radial cases: an observer inside the photon sphere)
-                                   draws no disk.  Follow-ups, not in this ABI: GEO_FLAG_RING_F64
-                                   on disk frames, GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS /
-                                   _COMPOSITE.
+                                   draws no disk.  The flag stays refused together with
+                                   GEO_FLAG_RING_F64; the capture band of a disk frame goes
+                                   through f64 by the context state geo_set_disk_ring_f64
+                                   (mask, UV, steps and steps_total are then the plain
+                                   GEO_FLAG_RING_F64 render's).  Follow-ups, not in this ABI:
+                                   GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE.
                                    With geo_set_disk_shift the hits are shaded by their
                                    Doppler and redshift factor. */
 #define GEO_FLAG_SS4 32u        /* (a build extension, not in the reference) 2 x 2 supersampling,
@@ -291,6 +296,34 @@ int geo_clear_disk(geo_ctx* ctx);
  * Consumed by the next render call whether it succeeds or not (the idiom of
  * geo_time_next_render); a render without GEO_FLAG_DISK writes nothing. */
 int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
+
+/* (GEO_HAS_DISK_RING_F64) The disk's capture band in f64: while on (on != 0),
+ * a GEO_FLAG_DISK render through geo_render_rows / _bands / _band_set
+ * (unshaded, shaded by geo_set_disk_shift, or the emission of
+ * geo_set_disk_emission; GEO_FLAG_DEFER_STEPS at most, as before) takes the
+ * pixels of the band |b/b_c - 1| < GEO_RING_X, GEO_FLAG_RING_F64's band decided
+ * on the f32 ray, through the f64 path: their traveled angle, mask, step count
+ * and the disk's crossing probes (csrc/geo_band.h band_lambda_disk states the
+ * rules).  A band pixel's hit radius is the f64 integrator's, rounded once to
+ * f32; everything after it (U, g, q, the samples, the blend) is the f32 code.
+ * Every other pixel is drawn as without the state, bit for bit.  mask, UV,
+ * steps and steps_total (or the deferred accumulator) are those of the plain
+ * GEO_FLAG_RING_F64 render: the same scene with GEO_FLAG_RING_F64 in place of
+ * GEO_FLAG_DISK.  All per-pixel outputs work (out_mask, out_uv, out_steps and
+ * the buffers of geo_disk_hits_next_render, geo_disk_shift_next_render and
+ * geo_disk_emission_next_render), as do geo_time_next_render, geo_set_dispatch
+ * (the learned order has a grid key of its own; a band pixel's steps count
+ * twice in a tile's cost, as in a GEO_FLAG_RING_F64 render) and
+ * geo_set_tile_order.  With rs == 0 there is no capture orbit: the state is
+ * ignored and the frame is the plain disk frame.  While on, what is colour-only
+ * or batched returns GEO_EINVAL for a disk scene, launches nothing and writes
+ * nothing (an armed per-pixel buffer is still consumed): GEO_FLAG_SS4 disk
+ * renders, geo_render_disk_batch, geo_render_ss_batch and
+ * geo_render_emission_batch (such a frame would come out without its band).
+ * Renders without GEO_FLAG_DISK are untouched, and GEO_FLAG_DISK |
+ * GEO_FLAG_RING_F64 stays GEO_EINVAL everywhere.  Off by default; kept across
+ * geo_set_disk, cleared by geo_clear_disk.  GEO_EINVAL for a NULL ctx. */
+int geo_set_disk_ring_f64(geo_ctx* ctx, int on);
 
 /* Doppler and redshift shading of the disk (csrc/geo_disk.h).  The disk's
  * matter moves on circular geodesics about spin * normal (spin = +1: the

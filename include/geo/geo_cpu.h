@@ -92,6 +92,32 @@ int geo_render_cpu_disk_emission(const geo_frame* frame, const geo_scene* scene,
                                  uint32_t disk_w, uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
                                  const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q);
 
+/* geo_render_cpu_disk_emission with the state of geo_set_disk_ring_f64
+ * (geo.h, GEO_HAS_DISK_RING_F64) as a trailing argument: ring_f64 != 0 takes
+ * the disk's band lanes (|b/b_c - 1| < GEO_RING_X on the f32 ray) through the
+ * f64 path of csrc/geo_band.h, under the device's rules: GEO_FLAG_SS4 with
+ * ring_f64 != 0 is GEO_EINVAL, GEO_FLAG_DISK | GEO_FLAG_RING_F64 stays
+ * GEO_EINVAL, and rs = 0 ignores it.  ring_f64 == 0 is
+ * geo_render_cpu_disk_emission.  Output equal to the GPU's bit for bit. */
+int geo_render_cpu_disk_ring_f64(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                 uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
+                                 uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                                 uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                                 unsigned long long* steps_total, const geo_disk* disk, const uint8_t* disk_rgba8,
+                                 uint32_t disk_w, uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                 const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q, int ring_f64);
+
+/* The same for the shaded render: geo_render_cpu_disk_shift with a trailing
+ * ring_f64 (ring_f64 == 0 is geo_render_cpu_disk_shift). */
+int geo_render_cpu_disk_shift_ring_f64(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                       uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                       uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                       uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                       float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                       const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                       uint32_t disk_h, float* out_hits, const geo_disk_shift* shift, float* out_g,
+                                       int ring_f64);
+
 #ifdef __cplusplus
 }
 #endif

@@ -316,6 +316,14 @@ struct ThinDisk {
         emitting = false;
         return *this;
     }
+    // The capture band's pixels in f64 (geo_set_disk_ring_f64): the third
+    // image's radii, and the colours that follow from them, to the disk's
+    // accuracy bar.  Off unless set_ring_f64 is called.
+    bool ring_f64 = false;
+    ThinDisk& set_ring_f64(bool on = true) {
+        ring_f64 = on;
+        return *this;
+    }
 };
 
 // ---- BasicSphereBuffer (basic_sphere_buffer.rs) -------------------------
@@ -368,6 +376,7 @@ class BasicSphereBuffer : public SchwarzschildSphereShaderDraw {
         check(geo_set_disk_emission(ctx_->get(), d.emitting ? &d.emission : nullptr, d.ramp.data(),
                                     (uint32_t)(d.ramp.size() / 4u)),
               "geo_set_disk_emission");
+        check(geo_set_disk_ring_f64(ctx_->get(), d.ring_f64 ? 1 : 0), "geo_set_disk_ring_f64");
         disk_ = true;
     }
 

@@ -40,6 +40,7 @@ GEO_HAS_DISK_BATCH = 1  # geo_render_disk_batch
 GEO_HAS_SS4_BATCH = 1  # geo_render_ss_batch
 GEO_HAS_DISK_EMISSION = 1  # geo_set_disk_emission, geo_disk_emission_next_render
 GEO_HAS_DISK_EMISSION_BATCH = 1  # geo_render_emission_batch
+GEO_HAS_DISK_RING_F64 = 1  # geo_set_disk_ring_f64
 GEO_DISK_PROFILE_POWER = 0
 GEO_DISK_PROFILE_THIN = 1
 GEO_DISK_RAMP_MAX = 1024
@@ -135,6 +136,7 @@ SIGNATURES = {
     "geo_disk_shift_next_render": (_int, [_vp, _vp]),
     "geo_set_disk_emission": (_int, [_vp, ctypes.POINTER(GeoDiskEmission), _vp, _u32]),
     "geo_disk_emission_next_render": (_int, [_vp, _vp]),
+    "geo_set_disk_ring_f64": (_int, [_vp, _int]),
     "geo_set_fan": (_int, [_vp, _vp, _u32]),
     "geo_solve_ray_fan": (_int, [_vp, _f64, _f64, _u32, _f64, _u32, _f64, _vp, _vp]),
     "geo_render_rows": (

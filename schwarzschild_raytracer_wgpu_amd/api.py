@@ -118,6 +118,7 @@ class Context:
         self._h = h
         self.device = device
         self.disk_emission_set = False  # set_disk_emission is on (dist.ShardedFrame asks)
+        self.disk_ring_f64 = False  # set_disk_ring_f64 is on (likewise)
 
     def close(self) -> None:
         h = getattr(self, "_h", None)
@@ -148,6 +149,7 @@ class Context:
     def clear_disk(self) -> None:
         check("geo_clear_disk", lib.geo_clear_disk(self._h))
         self.disk_emission_set = False
+        self.disk_ring_f64 = False
 
     def disk_hits_next_render(self, buf) -> None:
         """geo_disk_hits_next_render: the next render writes 3 x (r, U) floats per pixel
@@ -209,6 +211,15 @@ class Context:
         if buf.dtype != torch.float32:
             raise ValueError("buf must be float32")
         check("geo_disk_emission_next_render", lib.geo_disk_emission_next_render(self._h, _ptr(buf)))
+
+    def set_disk_ring_f64(self, on: bool = True) -> None:
+        """geo_set_disk_ring_f64: GEO_FLAG_DISK renders take the pixels of the capture band
+        (|b/b_c - 1| < GEO_RING_X, GEO_FLAG_RING_F64's band) through the f64 path, the disk's
+        crossing probes included: the third image's radii, and the colours that follow from
+        them, hold the disk's accuracy bar.  While on, supersampled and batched disk renders
+        are refused.  Kept across set_disk, cleared by clear_disk."""
+        check("geo_set_disk_ring_f64", lib.geo_set_disk_ring_f64(self._h, 1 if on else 0))
+        self.disk_ring_f64 = bool(on)
 
     def set_fan(self, fan: np.ndarray) -> None:
         a = np.ascontiguousarray(fan, dtype=np.float32)

@@ -56,6 +56,9 @@ struct CpuJob {
     geo::DiskEmission ek;
     const uint32_t* ramp;
     float* qs;
+    // geo_render_cpu_disk_ring_f64 (geo_set_disk_ring_f64): the disk's band
+    // lanes take the f64 path (`band` above holds its constants)
+    bool dring;
 };
 
 float geodesic(const CpuJob& j, float st, float ct, float rct, uint32_t* n) {
@@ -186,6 +189,57 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             geo::DiskRay dr;
             geo::disk_ray(j.dk, k, c2x, c2y, ct, rct, &dr);
             uint32_t n = 0;
+            if (j.dring) {
+                // geo_render_disk_ring_kernel per pixel: the band's lanes by
+                // the f64 path, the others as below, both through DiskHits
+                float lam;
+                bool bh;
+                geo::DiskHits h;
+                if (geo::in_band(j.band.kx, ct)) {
+                    const double l = geo::disk_hits_band(j.band, j.dk, dr, px, py, &n, &h);
+                    lam = (float)l;
+                    bh = l < (double)geo::kBlackHoleLambda;
+                } else {
+                    float Uk[geo::kDiskMaxCrossings];
+                    const float ang = geo::geodesic_kind(k) == geo::kCurvedOut
+                                          ? geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk)
+                                          : geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
+                    lam = geo::kPi2 - ang;
+                    bh = lam < geo::kBlackHoleLambda;
+                    geo::disk_hits_f32(j.dk, k, dr, Uk, n, ang, &h);
+                }
+                float U = 0.0f, V = 0.0f;
+                if (!bh || j.uv) geo::sky_uv(j.f->central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
+                const size_t o = (size_t)ly * j.width + px;
+                const uint32_t base = bh ? geo::kBlackRGBA : geo::sample_sky(fetch, j.sw, j.sh, j.opaque, U, V);
+                float* const hits = j.hits ? j.hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
+                float* const gs = j.gs ? j.gs + o * geo::kDiskMaxCrossings : nullptr;
+                float* const qs = j.qs ? j.qs + o * geo::kDiskMaxCrossings : nullptr;
+                if (j.emit) {
+                    auto rfetch = [p = j.ramp](uint32_t i) { return p[i]; };
+                    geo::DiskShiftRay sr;
+                    geo::disk_shift_ray(j.dk, j.ek.s, dr, ct, g_obs, &sr);
+                    j.rgba[o] = geo::disk_shade_hits(j.dk, dr, h, base,
+                                                     geo::disk_colour_emit(j.dk, k, j.ek, sr, dsample, rfetch), hits, gs,
+                                                     qs);
+                } else if (j.shift) {
+                    geo::DiskShiftRay sr;
+                    geo::disk_shift_ray(j.dk, j.sk, dr, ct, g_obs, &sr);
+                    j.rgba[o] = geo::disk_shade_hits(j.dk, dr, h, base, geo::disk_colour_shift(k, j.sk, sr, dsample),
+                                                     hits, gs, nullptr);
+                } else {
+                    j.rgba[o] = geo::disk_shade_hits(j.dk, dr, h, base, geo::disk_colour_plain(dsample), hits, nullptr,
+                                                     nullptr);
+                }
+                if (j.mask) j.mask[o] = bh ? 1 : 0;
+                if (j.uv) {
+                    j.uv[2 * o] = U;
+                    j.uv[2 * o + 1] = V;
+                }
+                if (j.steps) j.steps[o] = n;
+                total += n;
+                continue;
+            }
             float Uk[geo::kDiskMaxCrossings];
             float ang;
             switch (geo::geodesic_kind(k)) {
@@ -321,7 +375,8 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
                     float* out_uv, uint32_t* out_steps, unsigned long long* steps_total, const geo_disk* disk,
                     const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits,
                     const geo_disk_shift* shift, float* out_g, const geo_disk_emission* emission = nullptr,
-                    const uint8_t* ramp_rgba8 = nullptr, uint32_t ramp_n = 0, float* out_q = nullptr) {
+                    const uint8_t* ramp_rgba8 = nullptr, uint32_t ramp_n = 0, float* out_q = nullptr,
+                    bool ring_f64 = false) {
     if (!frame || !scene || !sky_rgba8 || !out_rgba8 || sky_w == 0 || sky_h == 0 || width == 0 || height == 0 ||
         row_step == 0 || width > (1u << 20) || height > (1u << 20))
         return GEO_EINVAL;
@@ -343,6 +398,8 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
                (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || out_mask || out_uv ||
                out_steps || out_hits || out_g || out_q || width > (1u << 19) || height > (1u << 19)))
         return GEO_EINVAL;
+    // geo_set_disk_ring_f64 (geo.h): not with GEO_FLAG_SS4
+    if (ring_f64 && ss) return GEO_EINVAL;
     const bool ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
         return GEO_EINVAL;
@@ -415,7 +472,9 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.uv = out_uv;
     j.steps = out_steps;
     j.ring = ring_flag && scene->rs > 0.0f && scene->r_obs > scene->rs;
-    if (j.ring) j.band = geo::band_consts(*frame, *scene, width, height);  // (never with GEO_FLAG_SS4)
+    // (no capture orbit, rs = 0: the state is ignored, the plain disk frame)
+    j.dring = disk && ring_f64 && scene->rs > 0.0f && scene->r_obs > scene->rs;
+    if (j.ring || j.dring) j.band = geo::band_consts(*frame, *scene, width, height);  // (never with GEO_FLAG_SS4)
     j.disk = disk != nullptr;
     j.dtex = nullptr;
     j.dw = disk_w;
@@ -534,4 +593,38 @@ extern "C" int geo_render_cpu_disk_emission(const geo_frame* frame, const geo_sc
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
                            disk_h, out_hits, nullptr, emission || ss ? out_g : nullptr, emission, ramp_rgba8, n,
                            emission || ss ? out_q : nullptr);
+}
+
+extern "C" int geo_render_cpu_disk_ring_f64(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                            uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                            uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                            uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                            float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                            const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                            uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                            const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q,
+                                            int ring_f64) {
+    if (!disk) return GEO_EINVAL;
+    const bool ss = scene && (scene->flags & GEO_FLAG_SS4) != 0;
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, nullptr, emission || ss ? out_g : nullptr, emission, ramp_rgba8, n,
+                           emission || ss ? out_q : nullptr, ring_f64 != 0);
+}
+
+extern "C" int geo_render_cpu_disk_shift_ring_f64(const geo_frame* frame, const geo_scene* scene,
+                                                  const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+                                                  const float* fan, uint32_t n_fan, uint32_t width, uint32_t height,
+                                                  uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                                                  uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
+                                                  uint32_t* out_steps, unsigned long long* steps_total,
+                                                  const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                                  uint32_t disk_h, float* out_hits, const geo_disk_shift* shift,
+                                                  float* out_g, int ring_f64) {
+    if (!disk) return GEO_EINVAL;
+    const bool ss = scene && (scene->flags & GEO_FLAG_SS4) != 0;
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, shift, shift || ss ? out_g : nullptr, nullptr, nullptr, 0, nullptr,
+                           ring_f64 != 0);
 }

@@ -292,4 +292,192 @@ GEO_HD double band_lambda(const BandConsts& k, uint32_t px, uint32_t py, uint32_
     return kHalfPi - band_steps(k, U, V, it, steps);
 }
 
+// ---- The band's lanes of a disk render (geo_set_disk_ring_f64) ----------
+// band_lambda with the thin disk's crossing probes (geo_disk.h) taken from the
+// f64 states: the same traveled angle and step count, bit for bit, and the
+// radius r of each crossing from the f64 integrator's U there.  For a lane of
+// the band:
+//   * crossing angles: disk_ray on the f32 ray, unchanged (a_k, cos phi,
+//     sin phi, sin a_0, cos a_0 are the f32 values, as the sky direction of a
+//     ring render is the f32 ray's); a_k = fma(k, pi, a_0) in f32, as disk_ray
+//     forms it, is widened to f64 exactly
+//   * node j_k = floor(min(a_k / h, 2^24)) with the IEEE f64 divide
+//     (h = BandConsts::h), partial step d_k = fma(-j_k, h, a_k)
+//   * U(a_k) = one band_rk4 from the f64 main loop's state at node j_k with
+//     step d_k, its constants formed as band_steps forms Newton's: d/2,
+//     d^2/4, d^2/2, d/6, d^2/6
+//   * the loop keeps band_lambda's groups of four with one exit branch; a
+//     group that holds a due node (j_k < it + 4) is handled as a group with an
+//     exit state is: it is replayed step by step, with band_steps' tests
+//     step for step and the probe of a node after the loop test that admits
+//     its step, and the groups go on after it.  Stepwise and grouped steps are
+//     the same band_rk4 on the same states, and a group without an exit state
+//     passes every test of band_steps, so the step count and the angle are
+//     band_lambda's
+//   * a crossing is probed exactly when j_k < the f64 step count: the loop
+//     test at node j_k passed, so the step that starts there was executed
+//     (and counted by every later exit)
+//   * the probe keeps r = (float)(scale / U) (the f64 scale = 3 rs/2, the IEEE
+//     divide, rounded once; three floats in place of three doubles across the
+//     loop); a crossing that was not probed keeps r = 0
+//   * crossing k is a hit (geo_disk.h disk_band_hit) when j_k < the step
+//     count (it was probed), a_k < the f64 traveled angle (GEO_NO_VALUE = 15
+//     > a_2 when the ray never crosses the sphere), U > 0 and r_in <= r <=
+//     r_out.  With r_in > 0 the last test holds the first and the third: an
+//     unprobed crossing has r = 0, U <= 0 gives r <= 0 or +-inf, a NaN fails
+//     every compare.  Everything after r is the f32 code
+//   * IEEE f64 + - * / sqrt fma only: the host build and the gfx950 kernel
+//     agree bit for bit, as band_lambda's do.
+// The probe slots are scalars and selects, as in geodesic_angle_disk (a store
+// at a per-lane slot index would put them in scratch memory).
+
+// band_lambda's set-up of pixel (px, py)'s ray, restated for band_lambda_disk
+// (band_lambda keeps its own copy: through a shared helper the ring kernels'
+// code came out different): the camera ray, the aberration and
+// solve_geodesic's cases before its loop.  True: the loop starts from the
+// scaled state (*U, *V); false: the ray ends here with the traveled angle
+// *early (a radial ray, a pre-filter).
+GEO_HD bool band_init(const BandConsts& k, uint32_t px, uint32_t py, double* U, double* V, double* early) {
+    // the camera ray and the aberration (pixel_central_dir in f64)
+    const double fx = (double)px, fy = (double)py;
+    const double dx = fma64_(fy, k.a[0], fma64_(fx, k.b[0], k.c[0]));
+    const double dy = fma64_(fy, k.a[1], fma64_(fx, k.b[1], k.c[1]));
+    const double dz = fma64_(fy, k.a[2], fma64_(fx, k.b[2], k.c[2]));
+    const double len = __builtin_sqrt(fma64_(dz, dz, fma64_(dy, dy, dx * dx)));
+    const double id = 1.0 / fma64_(-k.k, dz, len);
+    const double g = k.kt * id;
+    double ex = dx * g, ey = dy * g, ez = fma64_(-k.k, len, dz) * id;
+    if (!k.m1_identity) {
+        const double x = fma64_(k.m1[6], ez, fma64_(k.m1[3], ey, k.m1[0] * ex));
+        const double y = fma64_(k.m1[7], ez, fma64_(k.m1[4], ey, k.m1[1] * ex));
+        const double z = fma64_(k.m1[8], ez, fma64_(k.m1[5], ey, k.m1[2] * ex));
+        ex = x;
+        ey = y;
+        ez = z;
+    }
+    // sin and cos of theta (to_polar, shader.wgsl:75): sin clamped to [-1, 1]
+    const double st = ez > -1.0 ? (ez < 1.0 ? ez : 1.0) : -1.0;
+    const double ct = __builtin_sqrt(fma64_(ey, ey, ex * ex));
+    // solve_ray_fan's node (:38-49, r > rs) and solve_geodesic's set-up (:60-132)
+    const bool falling = st > 0.0;
+    const double rotation = k.r * ct;
+    if (rotation < 1e-10) {
+        *early = falling ? k.radial_falling : k.radial_outgoing;
+        return false;
+    }
+    const double b = rotation / k.energy;
+    const double ib2 = 1.0 / (b * b);
+    if (k.pf_always || ib2 < k.barrier_lim || (falling ? k.pf_falling : k.pf_outgoing)) {
+        *early = GEO_NO_VALUE;
+        return false;
+    }
+    const double ub = __builtin_sqrt(ib2 - k.hor);
+    *U = k.U0;
+    *V = k.scale * (falling ? ub : -ub);
+    return true;
+}
+
+constexpr double kBandMaxNode = 16777216.0;  // 2^24 >= max_steps: never due
+
+// crosses: the ray's plane cuts the disk's (DiskRay::jn[0] != 0xFFFFFFFF).
+// *angle: the f64 traveled angle (pi/2 - the returned lambda' before rounding).
+GEO_HD double band_lambda_disk(const BandConsts& k, uint32_t px, uint32_t py, float a0, bool crosses, uint32_t* steps,
+                               double* angle, float* r0, float* r1, float* r2) {
+    constexpr double kHalfPi = 1.57079632679489661923;
+    *steps = 0;
+    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
+    double U, V, ang;
+    if (band_init(k, px, py, &U, &V, &ang)) {
+        // the lane's next crossing: slot kc at node jt with partial step dt
+        const auto node = [&](uint32_t c, uint32_t* j, double* d) {
+            const float a = fmaf_((float)c, kPi, a0);
+            const double jf = __builtin_floor(__builtin_fmin((double)a / k.h, kBandMaxNode));
+            *j = crosses ? (uint32_t)jf : 0xFFFFFFFFu;
+            *d = fma64_(-jf, k.h, (double)a);
+        };
+        uint32_t kc = 0, jt;
+        double dt;
+        node(0u, &jt, &dt);
+        const auto probe = [&](double pu, double pv) {
+            const double d2 = dt * dt;
+            double wu, wv;
+            band_rk4(pu, pv, dt, dt / 2.0, d2 / 4.0, d2 / 2.0, dt / 6.0, d2 / 6.0, &wu, &wv);
+            const float rr = (float)(k.scale / wu);
+            p0 = kc == 0u ? rr : p0;
+            p1 = kc == 1u ? rr : p1;
+            p2 = kc == 2u ? rr : p2;
+            ++kc;
+            if (kc < 3u)
+                node(kc, &jt, &dt);
+            else
+                jt = 0xFFFFFFFFu;
+        };
+        uint32_t it = 0;
+        bool done = false;
+        ang = GEO_NO_VALUE;
+        *steps = k.max_steps;
+        while (!done && it < k.max_steps) {
+            // whole groups, until one holds an exit state or a due node
+            while (it + 4u <= k.max_steps) {
+                double u1, v1, u2, v2, u3, v3, u4, v4;
+                band_rk4(U, V, k.h, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &u1, &v1);
+                band_rk4(u1, v1, k.h, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &u2, &v2);
+                band_rk4(u2, v2, k.h, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &u3, &v3);
+                band_rk4(u3, v3, k.h, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &u4, &v4);
+                if ((int)band_group_out(k, u1, u2, u3, u4) | (int)(jt < it + 4u)) break;
+                U = u4;
+                V = v4;
+                it += 4u;
+            }
+            // that group (or the budget's tail of fewer than four steps),
+            // step by step: band_steps' loop with the probes
+            const uint32_t end = it + 4u <= k.max_steps ? it + 4u : k.max_steps;
+            for (; it < end; ++it) {
+                if ((U > k.HU && V > 0.0) || !(U > 0.0)) {  // the loop test (:134-135)
+                    *steps = it;
+                    done = true;
+                    break;
+                }
+                while (jt == it) probe(U, V);
+                double NU, NV;
+                band_rk4(U, V, k.h, k.hh, k.hh2, k.hhh, k.h6, k.h2_6, &NU, &NV);
+                if ((NU > k.SU) != (U > k.SU)) {
+                    // Newton on the step length from the steeper end (:150-182)
+                    double ns, wu, wv;
+                    if (__builtin_fabs(V) > __builtin_fabs(NV)) {
+                        ns = 0.0;
+                        wu = U;
+                        wv = V;
+                    } else {
+                        ns = k.h;
+                        wu = NU;
+                        wv = NV;
+                    }
+                    for (int n = 0; n < kNewtonIters; ++n) {
+                        ns -= (wu - k.SU) / wv;
+                        const double n2 = ns * ns;
+                        band_rk4(U, V, ns, ns / 2.0, n2 / 4.0, n2 / 2.0, ns / 6.0, n2 / 6.0, &wu, &wv);
+                    }
+                    *steps = it + 1u;
+                    ang = (double)it * k.h + ns;
+                    done = true;
+                    break;
+                }
+                if (NU < k.BD) {
+                    *steps = it + 1u;
+                    done = true;
+                    break;
+                }
+                U = NU;
+                V = NV;
+            }
+        }
+    }
+    *angle = ang;
+    *r0 = p0;
+    *r1 = p1;
+    *r2 = p2;
+    return kHalfPi - ang;
+}
+
 }  // namespace geo

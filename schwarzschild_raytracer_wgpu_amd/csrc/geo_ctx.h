@@ -125,6 +125,9 @@ struct geo_ctx {
     uint32_t* emit_ramp;
     uint32_t emit_n;
     float* q_next;
+    // geo_set_disk_ring_f64: the disk's band lanes in f64 (kept across
+    // geo_set_disk, cleared by geo_clear_disk)
+    bool disk_ring;
 #if defined(GEO_WAVE_LOG)
     unsigned long long* wave_log;  // diagnostic build only (geo_debug_set_wave_log)
 #endif

@@ -37,6 +37,7 @@
 
 #include <stdint.h>
 
+#include "geo_band.h"
 #include "geo_pixel.h"
 
 namespace geo {
@@ -586,6 +587,111 @@ GEO_HD uint32_t disk_shade_emit(const DiskConsts& d, const PixelConsts& k, const
     c = disk_shade_emit_slot_<1>(d, k, dr, em, sr, Uk[1], steps, angle, c, sample, fetch, hits, gs, qs);
     c = disk_shade_emit_slot_<0>(d, k, dr, em, sr, Uk[0], steps, angle, c, sample, fetch, hits, gs, qs);
     return c;
+}
+
+// ---- The capture band's lanes in f64 (geo_set_disk_ring_f64) -------------
+// While the state is on, a lane of the band |b/b_c - 1| < GEO_RING_X
+// (geo::in_band on the f32 ray, GEO_FLAG_RING_F64's own test) takes its
+// traveled angle, mask, step count and crossing probes from the f64 path
+// (geo_band.h band_lambda_disk, which states the lane's rules); every other
+// lane does what it does without the state.  Both kinds of lane meet in
+// DiskHits, a ray's three crossings as (hit, r): the f32 lane's by disk_hit's
+// own test and radius, the band lane's by the f64 hit rule with r rounded
+// once to f32.  Everything after r (Ud, Vd, g, q, the samples and the
+// far-to-near blend) is the f32 code above on that r.
+struct DiskHits {
+    bool hit[kDiskMaxCrossings];
+    float r[kDiskMaxCrossings];  // (read only where hit)
+};
+
+// An f32 lane's crossings: disk_hit's test and radius.
+GEO_HD void disk_hits_f32(const DiskConsts& d, const PixelConsts& k, const DiskRay& dr,
+                          const float (&Uk)[kDiskMaxCrossings], uint32_t steps, float angle, DiskHits* h) {
+#pragma unroll
+    for (int c = 0; c < kDiskMaxCrossings; ++c) {
+        h->hit[c] = (dr.jn[c] < steps) & (dr.ak[c] < angle) & (med3_(Uk[c], d.u_lo, d.u_hi) == Uk[c]);
+        h->r[c] = k.scale * rcpf_(Uk[c]);
+    }
+}
+
+// A band lane's crossing from the f64 probe's radius rr (0: not probed, its
+// node was never reached) and the f64 traveled angle (geo_band.h: r_in > 0, so
+// the annulus test holds "probed" and "U > 0" too).
+GEO_HD void disk_band_hit(const DiskConsts& d, float ak, float rr, double angle, bool* hit, float* r) {
+    *hit = ((double)ak < angle) & (d.r_in <= rr) & (rr <= d.r_out);
+    *r = rr;
+}
+
+// A band lane's pixel: lambda' in f64 (band_lambda's), its steps and crossings.
+GEO_HD double disk_hits_band(const BandConsts& bk, const DiskConsts& d, const DiskRay& dr, uint32_t px, uint32_t py,
+                             uint32_t* steps, DiskHits* h) {
+    double angle;
+    float r0, r1, r2;
+    const float a0 = dr.ak[0];  // (a_k = fma(k, pi, a_0), disk_ray's own values)
+    const double l = band_lambda_disk(bk, px, py, a0, dr.jn[0] != 0xFFFFFFFFu, steps, &angle, &r0, &r1, &r2);
+    disk_band_hit(d, a0, r0, angle, &h->hit[0], &h->r[0]);
+    disk_band_hit(d, fmaf_(1.0f, kPi, a0), r1, angle, &h->hit[1], &h->r[1]);
+    disk_band_hit(d, fmaf_(2.0f, kPi, a0), r2, angle, &h->hit[2], &h->r[2]);
+    return l;
+}
+
+// disk_shade_slot_ and its shaded forms on a crossing of DiskHits.
+// colour(r, Ud, Vd, &g, &q): the hit's colour (the texture sample, shifted or
+// turned into the emission's; g and q written where the render has them).
+template <int S, typename Colour>
+GEO_HD uint32_t disk_shade_hits_slot_(const DiskConsts& d, const DiskRay& dr, const DiskHits& h, uint32_t c,
+                                      const Colour& colour, float* hits, float* gs, float* qs) {
+    float r = 0.0f, Ud = 0.0f, g = 0.0f, q = 0.0f;
+    if (h.hit[S]) {
+        r = h.r[S];
+        const float sg = (S & 1) ? -1.0f : 1.0f;
+        const float sa = sg * dr.sa, ca = sg * dr.ca;
+        const float X = fmaf_(sa, fmaf_(d.ex[0], dr.cphi, d.ex[1] * dr.sphi), ca * d.ex[2]);
+        const float Y = fmaf_(sa, fmaf_(d.ey[0], dr.cphi, d.ey[1] * dr.sphi), ca * d.ey[2]);
+        Ud = med3_(atan2_turns_(Y, X), 0.0f, 1.0f);
+        const float Vd = med3_((r - d.r_in) * d.inv_dr, 0.0f, 1.0f);
+        c = composite_(colour(r, Ud, Vd, &g, &q), c);
+    }
+    if (hits) {
+        hits[2 * S] = r;
+        hits[2 * S + 1] = Ud;
+    }
+    if (gs) gs[S] = g;
+    if (qs) qs[S] = q;
+    return c;
+}
+
+template <typename Colour>
+GEO_HD uint32_t disk_shade_hits(const DiskConsts& d, const DiskRay& dr, const DiskHits& h, uint32_t base,
+                                const Colour& colour, float* hits, float* gs, float* qs) {
+    static_assert(kDiskMaxCrossings == 3, "three slots, written out");
+    uint32_t c = base;
+    c = disk_shade_hits_slot_<2>(d, dr, h, c, colour, hits, gs, qs);
+    c = disk_shade_hits_slot_<1>(d, dr, h, c, colour, hits, gs, qs);
+    c = disk_shade_hits_slot_<0>(d, dr, h, c, colour, hits, gs, qs);
+    return c;
+}
+
+// The three renders' colours for disk_shade_hits.
+template <typename Sample>
+GEO_HD auto disk_colour_plain(const Sample& sample) {
+    return [&sample](float, float Ud, float Vd, float*, float*) { return sample(Ud, Vd); };
+}
+template <typename Sample>
+GEO_HD auto disk_colour_shift(const PixelConsts& k, const DiskShift& sh, const DiskShiftRay& sr, const Sample& sample) {
+    return [&k, &sh, &sr, &sample](float r, float Ud, float Vd, float* g, float*) {
+        *g = disk_shift_g(k, sr, r);
+        return disk_shift_colour(sh, *g, sample(Ud, Vd));
+    };
+}
+template <typename Sample, typename Fetch>
+GEO_HD auto disk_colour_emit(const DiskConsts& d, const PixelConsts& k, const DiskEmission& em, const DiskShiftRay& sr,
+                             const Sample& sample, const Fetch& fetch) {
+    return [&d, &k, &em, &sr, &sample, &fetch](float r, float Ud, float Vd, float* g, float* q) {
+        *g = disk_shift_g(k, sr, r);
+        *q = disk_emission_q(d, em, *g, r);
+        return disk_emission_colour(em, *q, sample(Ud, Vd), fetch);
+    };
 }
 
 }  // namespace geo

@@ -258,6 +258,7 @@ int geo_clear_disk(geo_ctx* c) {
     c->disk_set = false;
     c->shift_set = false;
     c->emit_set = false;
+    c->disk_ring = false;
     return GEO_OK;
 }
 
@@ -300,6 +301,12 @@ int geo_set_disk(geo_ctx* c, const geo_disk* disk, const uint8_t* rgba8, uint32_
     c->disk_h = h;
     c->disk = *disk;
     c->disk_set = true;
+    return GEO_OK;
+}
+
+int geo_set_disk_ring_f64(geo_ctx* c, int on) {
+    if (!c) return GEO_EINVAL;
+    c->disk_ring = on != 0;
     return GEO_OK;
 }
 
@@ -607,6 +614,43 @@ static int launch_disk(const RenderArgs& a, const FrameK& fk, const DiskArgs& d,
     });
 }
 
+// The same frame with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel):
+// the band's constants ride as a further argument.  The curved kinds only (a
+// capture orbit needs rs > 0).
+static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskVarArgs<kDiskEmit>) +
+                      sizeof(BandArg<true>) <= 4096,
+              "kernel arguments fit 4 KiB");
+template <int KIND>
+static int launch_disk_ring(const RenderArgs& a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh,
+                            const DiskEmitArgs* em, const geo::BandConsts& band, const LaunchPlan& p) {
+    if constexpr (KIND == geo::kFlat) {
+        return GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
+    } else {
+        FrameBatch<1> fb;
+        fb.f[0] = fk;
+        BandArg<true> bk;
+        bk.k = band;
+        return launch_split(a, p, wave_block_max_ny(p.tiles_x),
+                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+            const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
+            if (em) {
+                DiskVarArgs<kDiskEmit> x;
+                x.em = *em;
+                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskEmit>), grid, block, 0, p.s, start, stop,
+                                      0, la, fb, d, x, bk);
+            } else if (sh) {
+                DiskVarArgs<kDiskShift> x;
+                x.sh = *sh;
+                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskShift>), grid, block, 0, p.s, start,
+                                      stop, 0, la, fb, d, x, bk);
+            } else {
+                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskPlain>), grid, block, 0, p.s, start,
+                                      stop, 0, la, fb, d, DiskVarArgs<kDiskPlain>{}, bk);
+            }
+        });
+    }
+}
+
 // The batched disk launch (geo_render_disk_batch_kernel), the frames in
 // grid.z.  The one-frame disk render's wave-block grid, not the plain batch's
 // 32 x 8-pixel workgroups: a disk wave holds more registers than a plain one,
@@ -712,6 +756,7 @@ struct RenderWork {
     bool disk, ring_flag, mips, adaptive, defer;  // what the scene asks for (check_scene)
     bool ss;  // GEO_FLAG_SS4: the kernels' frame is the sample frame, twice the call's in width, height and rows
     bool ring;                                    // ring_flag and a capture orbit to draw (fill_frames)
+    bool disk_ring;  // a disk frame with geo_set_disk_ring_f64 on and a capture orbit to draw (check_scene)
     FrameK fk[kMaxBatchFrames];
     geo::PixelConsts pk[kMaxBatchFrames];
     RenderArgs a;
@@ -764,6 +809,12 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // its emission: refused, nothing launched)
     w.emit = w.disk && c->emit_set;
     if (w.emit && (rc.disk_batch || rc.ss_batch)) return GEO_EINVAL;
+    // geo_set_disk_ring_f64: the one-frame entry points' per-pixel renders
+    // only (a supersampled or batched disk frame would come out without its
+    // band: refused, nothing launched)
+    if (w.disk && c->disk_ring && (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch)) return GEO_EINVAL;
+    // (no capture orbit, rs = 0: the state is ignored, the plain disk frame)
+    w.disk_ring = w.disk && c->disk_ring && scene->rs > 0.0f && scene->r_obs > scene->rs;
     w.ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
     if (w.ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
         return GEO_EINVAL;
@@ -923,10 +974,11 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if (c->dispatch_mode != GEO_DISPATCH_LONGEST_FIRST) return GEO_OK;
     // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost
     // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's; an
-    // emission render has a key of its own, as the disk render has)
+    // emission render has a key of its own, as the disk render has, and a
+    // disk render with geo_set_disk_ring_f64 on, for its band's tiles)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
                              (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u) |
-                                 (w.emit ? 16u : 0u),
+                                 (w.emit ? 16u : 0u) | (w.disk_ring ? 32u : 0u),
                              tiles_x * tiles_y};
     if (!c->learn_valid || std::memcmp(key, c->learn_key, sizeof(key)) != 0) {
         std::memcpy(c->learn_key, key, sizeof(key));
@@ -1021,7 +1073,12 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
     }
     DiskEmitArgs em;
     if (w.emit) em = emit_args(c, rc, w);
+    geo::BandConsts band_k;
+    if (w.disk_ring) band_k = geo::band_consts(rc.frames[0], *rc.scene, rc.width, rc.height);
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        if (w.disk_ring)
+            return launch_disk_ring<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
+                                                           w.emit ? &em : nullptr, band_k, w.p);
         return launch_disk<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
                                                   w.emit ? &em : nullptr, w.p);
     });

@@ -257,6 +257,7 @@ class ShardedFrame:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
         if self.batch:
             self._refuse_emission_batch(scene)
+            self._refuse_ring_batch(scene)
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
         self.pending_scenes = []     # and copies of their scenes (they differ in r_obs at most)
         self._pending_key = b""
@@ -358,6 +359,17 @@ class ShardedFrame:
                              "entry points: pass emission_batch=True (geo_render_emission_batch), or use "
                              "batch_launch=False, or clear_disk_emission()")
 
+    def _refuse_ring_batch(self, scene) -> None:
+        """No batched entry point draws a disk frame's f64 band
+        (geo_set_disk_ring_f64, geo.h): a GEO_FLAG_DISK scene of a context
+        with set_disk_ring_f64 on is refused here, by name, instead of by the
+        launch's GEO_EINVAL."""
+        from ._lib import GEO_FLAG_DISK
+
+        if scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_ring_f64", False):
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_ring_f64 on: the batched entry "
+                             "points refuse it; use batch_launch=False, or set_disk_ring_f64(False)")
+
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
         """The frames of batch buffer b (slots first .. first + len(frames) - 1)
@@ -387,6 +399,7 @@ class ShardedFrame:
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
         self._refuse_emission_batch(scenes[0])
+        self._refuse_ring_batch(scenes[0])
         if self.emission_batch and self._emission_scene(scenes[0]):
             name = "geo_render_emission_batch"  # (with GEO_FLAG_SS4 or without)
         elif scenes[0].flags & GEO_FLAG_SS4:

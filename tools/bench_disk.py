@@ -58,6 +58,19 @@ side's spread ((max - min) / median of its alternation medians), the margin
 shaded batch.  --sessions (2) sessions go into one JSON object.
 
   python tools/bench_disk.py --batch 8 --emission [--out profiles/disk_emission_batch_bench_cfg3.json]
+
+--ring measures the disk frame with the capture band in f64
+(geo_set_disk_ring_f64) against the same frame with the state off, by
+--emission's method: --alternations (5) times --n (30) event-timed dispatches
+of each kind in blocks, after --settle (4) alternations of the same form that
+are reported apart, each kind on its own context.  The plain frame with and
+without GEO_FLAG_RING_F64 runs beside them in the same alternations: the plain
+frame's own ring cost is the second yardstick.  It reports the medians over
+the alternations, disk-on over disk-off and ring over plain, each off side's
+spread ((max - min) / median of its alternation medians) and whether each
+cost lies beyond twice that spread.  One JSON object.
+
+  python tools/bench_disk.py --ring [--out profiles/disk_ring_bench_cfg3.json]
 """
 from __future__ import annotations
 
@@ -77,6 +90,9 @@ def main():
     p.add_argument("--shift", action="store_true", help="also time the Doppler-shaded disk frame")
     p.add_argument("--emission", action="store_true",
                    help="time the blackbody emission frame against the shaded disk frame, in alternating blocks")
+    p.add_argument("--ring", action="store_true",
+                   help="time the disk frame with geo_set_disk_ring_f64 on against off, and the plain frame with and "
+                        "without GEO_FLAG_RING_F64, in alternating blocks")
     p.add_argument("--alternations", type=int, default=5, help="with --emission: blocks of --n renders of each kind")
     p.add_argument("--settle", type=int, default=4,
                    help="with --emission: alternations run first in the timed form, reported apart and not counted")
@@ -90,13 +106,16 @@ def main():
     p.add_argument("--out")
     args = p.parse_args()
     if not args.out:
-        name = "disk_emission_batch_bench_cfg3.json" if args.batch and args.emission else (
+        name = "disk_ring_bench_cfg3.json" if args.ring else "disk_emission_batch_bench_cfg3.json" if (
+            args.batch and args.emission) else (
             "disk_batch_bench_cfg3.json") if args.batch else (
             "disk_emission_bench_cfg3.json" if args.emission else (
                 "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json"))
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.ring:
+        return ring_main(args)
     if args.batch and args.emission:
         return emission_batch_main(args)
     if args.batch:
@@ -287,6 +306,104 @@ def emission_main(args):
     doc.append(res)
     with open(args.out, "w") as f:
         f.write(json.dumps(doc, indent=1) + "\n")
+
+
+def ring_main(args):
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg = CONFIGS["cfg3_4k"]
+    W, H = cfg.width, cfg.height
+    obs = g.Observer(cfg.rs, cfg.fov, W, H)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    r = obs.get_radial_position()
+    scenes = {"plain": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg.step, cfg.max_steps),
+              "plain_ring": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg.step, cfg.max_steps,
+                                         flags=_lib.GEO_FLAG_RING_F64),
+              "disk_off": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg.step, cfg.max_steps, flags=_lib.GEO_FLAG_DISK)}
+    scenes["disk_on"] = scenes["disk_off"]
+    r_in, r_out = 1.6 * cfg.rs, 2.2 * cfg.rs
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    # (each kind on its own context: the learned dispatch order is kept per context)
+    ctxs = {}
+    for kind in ("disk_off", "disk_on", "plain", "plain_ring"):
+        c = g.Context(0)
+        c.set_sky(sky)
+        if kind.startswith("disk"):
+            c.set_disk(tex, r_in, r_out)
+            c.set_disk_ring_f64(kind == "disk_on")
+        ctxs[kind] = c
+    dev = torch.device("cuda:0")
+    out = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)
+    for _ in range(args.warmup):
+        for kind, c in ctxs.items():
+            c.render_rows(frame, scenes[kind], W, H, 0, H, out)
+    torch.cuda.synchronize()
+    blocks, settling = [], []
+    for alt in range(args.settle + args.alternations):
+        med = {}
+        for kind, c in ctxs.items():
+            ev = []
+            for _ in range(args.n):
+                a, b = HipEvent(), HipEvent()
+                c.time_next_render(a, b)
+                c.render_rows(frame, scenes[kind], W, H, 0, H, out)
+                ev.append((a, b))
+            torch.cuda.synchronize()
+            ms = np.array([a.elapsed_time(b) for a, b in ev])
+            med[kind + "_ms_median"] = float(np.median(ms))
+            med[kind + "_ms_min"] = float(ms.min())
+            med[kind + "_ms_iqr"] = float(np.subtract(*np.percentile(ms, [75, 25])))
+        med["disk_on_over_off"] = med["disk_on_ms_median"] / med["disk_off_ms_median"]
+        med["plain_ring_over_plain"] = med["plain_ring_ms_median"] / med["plain_ms_median"]
+        (settling if alt < args.settle else blocks).append(med)
+    # what the two disk frames draw (two more renders, untimed): the state-on frame's hits, both step totals
+    hits = torch.zeros(W * H * 6, dtype=torch.float32, device=dev)
+    total_on = torch.zeros(1, dtype=torch.int64, device=dev)
+    total_off = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctxs["disk_on"].disk_hits_next_render(hits)
+    ctxs["disk_on"].render_rows(frame, scenes["disk_on"], W, H, 0, H, out, None, None, None, total_on)
+    ctxs["disk_off"].render_rows(frame, scenes["disk_off"], W, H, 0, H, out, None, None, None, total_off)
+    torch.cuda.synchronize()
+    hv = hits.view(H, W, 3, 2)[..., 0] > 0
+    for c in ctxs.values():
+        c.close()
+    m = {k: np.array([b[k + "_ms_median"] for b in blocks]) for k in ctxs}
+    spread = {k: float((m[k].max() - m[k].min()) / np.median(m[k])) for k in ("disk_off", "plain")}
+    on_off = float(np.median(m["disk_on"]) / np.median(m["disk_off"]))
+    ring_plain = float(np.median(m["plain_ring"]) / np.median(m["plain"]))
+    res = {
+        "config": "cfg3_4k", "width": W, "height": H, "max_steps": cfg.max_steps, "disk": [r_in, r_out],
+        "n": args.n, "warmup": args.warmup, "settling_alternations_not_counted": settling, "alternations": blocks,
+        **{k + "_ms_median": float(np.median(v)) for k, v in m.items()},
+        "disk_on_over_off": on_off,
+        "disk_on_over_off_min": float(min(b["disk_on_over_off"] for b in blocks)),
+        "disk_on_over_off_max": float(max(b["disk_on_over_off"] for b in blocks)),
+        "disk_off_alternation_spread": spread["disk_off"],
+        "disk_cost_beyond_twice_the_spread": bool(abs(on_off - 1.0) > 2.0 * spread["disk_off"]),
+        "plain_ring_over_plain": ring_plain,
+        "plain_alternation_spread": spread["plain"],
+        "plain_cost_beyond_twice_the_spread": bool(abs(ring_plain - 1.0) > 2.0 * spread["plain"]),
+        "hit_pixels_per_slot": [int(hv[..., k].sum()) for k in range(3)],
+        "steps_total_on": int(total_on.item()), "steps_total_off": int(total_off.item()),
+        "timing": "geo_time_next_render event pairs on each kernel dispatch; blocks of n renders of the disk frame with "
+                  "the state off, with it on, the plain frame and the plain GEO_FLAG_RING_F64 frame alternate in one "
+                  "process, each kind on its own context; spread = (max - min) / median of a kind's alternation medians",
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
 
 
 def batch_main(args):

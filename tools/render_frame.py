@@ -9,6 +9,7 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
         [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
+        [--disk-ring-f64]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -23,6 +24,9 @@ T_HI EXPOSURE colours the disk by its observed blackbody temperature
 for matter orbiting about --disk-spin * normal, a 256-entry
 scenes.blackbody_ramp from T_LO to T_HI, brightness EXPOSURE (T_obs/T_REF)**4);
 it takes the place of --disk-shift and works with --cpu and --ss.
+--disk-ring-f64 takes the pixels of the capture band through the f64 path
+(geo_set_disk_ring_f64: the third image's radii and colours to the disk's
+accuracy bar), on the GPU or with --cpu, not with --ss.
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -76,20 +80,21 @@ def disk_frame(args):
                   tex.shape[1], tex.shape[0], None]
         base = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, u32,
                 u32, vp]
+        ring = 1 if args.disk_ring_f64 else 0
         if emission is not None:
-            name = "geo_render_cpu_disk_emission"
-            lib.geo_render_cpu_disk_emission.restype = ctypes.c_int
-            lib.geo_render_cpu_disk_emission.argtypes = base + [vp, vp, u32, vp, vp]
-            rc = lib.geo_render_cpu_disk_emission(*common, ctypes.addressof(emission), ramp.ctypes.data, ramp.shape[0],
-                                                  None, None)
+            name = "geo_render_cpu_disk_ring_f64"
+            lib.geo_render_cpu_disk_ring_f64.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_ring_f64.argtypes = base + [vp, vp, u32, vp, vp, ctypes.c_int]
+            rc = lib.geo_render_cpu_disk_ring_f64(*common, ctypes.addressof(emission), ramp.ctypes.data, ramp.shape[0],
+                                                  None, None, ring)
         else:
-            name = "geo_render_cpu_disk_shift"
+            name = "geo_render_cpu_disk_shift_ring_f64"
             shift = None
             if args.disk_shift:
                 shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
-            lib.geo_render_cpu_disk_shift.restype = ctypes.c_int
-            lib.geo_render_cpu_disk_shift.argtypes = base + [vp, vp]
-            rc = lib.geo_render_cpu_disk_shift(*common, ctypes.addressof(shift) if shift else None, None)
+            lib.geo_render_cpu_disk_shift_ring_f64.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_shift_ring_f64.argtypes = base + [vp, vp, ctypes.c_int]
+            rc = lib.geo_render_cpu_disk_shift_ring_f64(*common, ctypes.addressof(shift) if shift else None, None, ring)
         if rc != 0:
             raise SystemExit(f"{name}: {rc}")
     else:
@@ -103,6 +108,8 @@ def disk_frame(args):
         if emission is not None:
             ctx.set_disk_emission(ramp, emission.t_ref, emission.t_lo, emission.t_hi, emission.profile,
                                   emission.exposure, emission.spin)
+        if args.disk_ring_f64:
+            ctx.set_disk_ring_f64(True)
         rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
         ctx.render_rows(frame, scene, w, h, 0, h, rgba)
     if args.out.endswith(".ppm"):
@@ -141,12 +148,16 @@ def main():
                    help="with --disk: blackbody emission (geo_set_disk_emission), in place of --disk-shift")
     p.add_argument("--disk-profile", choices=("power", "thin"), default="thin", help="with --disk-emission")
     p.add_argument("--disk-spin", type=int, choices=(1, -1), default=1, help="with --disk-emission")
+    p.add_argument("--disk-ring-f64", action="store_true",
+                   help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); not with --ss")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
     p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
     p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
     p.add_argument("--fov", type=float, default=math.pi / 2, help="with --disk")
     args = p.parse_args()
+    if args.disk_ring_f64 and (not args.disk or args.ss):
+        p.error("--disk-ring-f64 goes with --disk and without --ss (a supersampled disk frame refuses the state)")
     if args.disk:
         return disk_frame(args)
     if args.ss:
