@@ -514,6 +514,18 @@ static int launch_split(RenderArgs a, const LaunchPlan& p, uint32_t max_ny, F&& 
     return GEO_OK;
 }
 
+// A render of nframes frames on WB's 1-D grid (wave_blocks): one wave per
+// workgroup, the frame in grid.z; the kernel takes RenderArgs and then args.
+template <typename K, typename... Args>
+static int launch_wave_blocks(const RenderArgs& a, const LaunchPlan& p, uint32_t nframes, K kernel,
+                              const Args&... args) {
+    return launch_split(a, p, wave_block_max_ny(p.tiles_x),
+                        [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
+        const dim3 grid(wave_block_count(la.launch_tiles), 1, nframes), block(64);
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, p.s, start, stop, 0, la, args...);
+    });
+}
+
 // The launch of geo_render_kernel's instantiation for NF frames.  band:
 // GEO_FLAG_RING_F64's constants, or null; the ring kernels exist out of fan
 // mode and for the curved kinds only (kFlat has no capture orbit), and with
@@ -600,18 +612,9 @@ static int launch_disk(const RenderArgs& a, const FrameK& fk, const DiskArgs& d,
                        const DiskEmitArgs* em, const LaunchPlan& p) {
     FrameBatch<1> fb;
     fb.f[0] = fk;
-    return launch_split(a, p, wave_block_max_ny(p.tiles_x),
-                        [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-        const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
-        if (em)
-            hipExtLaunchKernelGGL(geo_render_disk_emit_kernel<KIND>, grid, block, 0, p.s, start, stop, 0, la, fb, d,
-                                  *em);
-        else if (sh)
-            hipExtLaunchKernelGGL(geo_render_disk_shift_kernel<KIND>, grid, block, 0, p.s, start, stop, 0, la, fb, d,
-                                  *sh);
-        else
-            hipExtLaunchKernelGGL(geo_render_disk_kernel<KIND>, grid, block, 0, p.s, start, stop, 0, la, fb, d);
-    });
+    if (em) return launch_wave_blocks(a, p, 1, geo_render_disk_emit_kernel<KIND>, fb, d, *em);
+    if (sh) return launch_wave_blocks(a, p, 1, geo_render_disk_shift_kernel<KIND>, fb, d, *sh);
+    return launch_wave_blocks(a, p, 1, geo_render_disk_kernel<KIND>, fb, d);
 }
 
 // The same frame with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel):
@@ -630,24 +633,18 @@ static int launch_disk_ring(const RenderArgs& a, const FrameK& fk, const DiskArg
         fb.f[0] = fk;
         BandArg<true> bk;
         bk.k = band;
-        return launch_split(a, p, wave_block_max_ny(p.tiles_x),
-                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-            const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
-            if (em) {
-                DiskVarArgs<kDiskEmit> x;
-                x.em = *em;
-                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskEmit>), grid, block, 0, p.s, start, stop,
-                                      0, la, fb, d, x, bk);
-            } else if (sh) {
-                DiskVarArgs<kDiskShift> x;
-                x.sh = *sh;
-                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskShift>), grid, block, 0, p.s, start,
-                                      stop, 0, la, fb, d, x, bk);
-            } else {
-                hipExtLaunchKernelGGL((geo_render_disk_ring_kernel<KIND, kDiskPlain>), grid, block, 0, p.s, start,
-                                      stop, 0, la, fb, d, DiskVarArgs<kDiskPlain>{}, bk);
-            }
-        });
+        if (em) {
+            DiskVarArgs<kDiskEmit> x;
+            x.em = *em;
+            return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskEmit>, fb, d, x, bk);
+        }
+        if (sh) {
+            DiskVarArgs<kDiskShift> x;
+            x.sh = *sh;
+            return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskShift>, fb, d, x, bk);
+        }
+        return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskPlain>, fb, d,
+                                  DiskVarArgs<kDiskPlain>{}, bk);
     }
 }
 
@@ -659,16 +656,8 @@ static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) <= 4096, "kernel argume
 template <int KIND>
 static int launch_disk_batch(const RenderArgs& a, const DiskBatchArgs& db, uint32_t nframes, bool shift,
                              const LaunchPlan& p) {
-    return launch_split(a, p, wave_block_max_ny(p.tiles_x),
-                        [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-        const dim3 grid(wave_block_count(la.launch_tiles), 1, nframes), block(64);
-        if (shift)
-            hipExtLaunchKernelGGL(geo_render_disk_batch_kernel<KIND, true>, grid, block, 0, p.s, start, stop, 0, la,
-                                  db);
-        else
-            hipExtLaunchKernelGGL(geo_render_disk_batch_kernel<KIND, false>, grid, block, 0, p.s, start, stop, 0, la,
-                                  db);
-    });
+    if (shift) return launch_wave_blocks(a, p, nframes, geo_render_disk_batch_kernel<KIND, true>, db);
+    return launch_wave_blocks(a, p, nframes, geo_render_disk_batch_kernel<KIND, false>, db);
 }
 }
 
@@ -1109,32 +1098,25 @@ static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderW
     fb.f[0] = w.fk[0];
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
-        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
-                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-            const dim3 grid(wave_block_count(la.launch_tiles)), block(64);
-            if (!w.disk) {
-                SsArgs<kSsPlain> xp;
-                xp.out_width = x.out_width;
-                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsPlain>), grid, block, 0, w.p.s, start, stop, 0, la,
-                                      fb, xp);
-            } else if (w.emit) {
-                SsEmitArgs xe;
-                xe.out_width = x.out_width;
-                xe.d = x.d;
-                xe.em = emit_args(c, rc, w);  // (SS4 is colour only: out_g and out_q are null here)
-                hipExtLaunchKernelGGL(geo_render_ss_emit_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0, la, fb,
-                                      xe);
-            } else if (!c->shift_set) {
-                SsArgs<kSsDisk> xd;
-                xd.out_width = x.out_width;
-                xd.d = x.d;
-                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsDisk>), grid, block, 0, w.p.s, start, stop, 0, la,
-                                      fb, xd);
-            } else {
-                hipExtLaunchKernelGGL((geo_render_ss_kernel<KIND, kSsDiskShift>), grid, block, 0, w.p.s, start, stop, 0,
-                                      la, fb, x);
-            }
-        });
+        if (!w.disk) {
+            SsArgs<kSsPlain> xp;
+            xp.out_width = x.out_width;
+            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsPlain>, fb, xp);
+        }
+        if (w.emit) {
+            SsEmitArgs xe;
+            xe.out_width = x.out_width;
+            xe.d = x.d;
+            xe.em = emit_args(c, rc, w);  // (SS4 is colour only: out_g and out_q are null here)
+            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_emit_kernel<KIND>, fb, xe);
+        }
+        if (!c->shift_set) {
+            SsArgs<kSsDisk> xd;
+            xd.out_width = x.out_width;
+            xd.d = x.d;
+            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsDisk>, fb, xd);
+        }
+        return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsDiskShift>, fb, x);
     });
 }
 
@@ -1236,19 +1218,10 @@ static int launch_ss_frames(const geo_ctx* c, const RenderCall& rc, const Render
     }
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
-        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
-                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-            const dim3 grid(wave_block_count(la.launch_tiles), 1, rc.nframes), block(64);
-            if (!w.disk)
-                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsPlain>), grid, block, 0, w.p.s, start, stop,
-                                      0, la, fb, x);
-            else if (!c->shift_set)
-                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsDisk>), grid, block, 0, w.p.s, start, stop,
-                                      0, la, db, x);
-            else
-                hipExtLaunchKernelGGL((geo_render_ss_batch_kernel<KIND, kSsDiskShift>), grid, block, 0, w.p.s, start,
-                                      stop, 0, la, db, x);
-        });
+        if (!w.disk) return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsPlain>, fb, x);
+        if (!c->shift_set)
+            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsDisk>, db, x);
+        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsDiskShift>, db, x);
     });
 }
 
@@ -1266,16 +1239,8 @@ static int launch_emit_frames(const geo_ctx* c, const RenderCall& rc, const Rend
     x.out_width = rc.width;
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
-        return launch_split(w.a, w.p, wave_block_max_ny(w.p.tiles_x),
-                            [&](const RenderArgs& la, uint32_t, hipEvent_t start, hipEvent_t stop) {
-            const dim3 grid(wave_block_count(la.launch_tiles), 1, rc.nframes), block(64);
-            if (w.ss)
-                hipExtLaunchKernelGGL(geo_render_ss_emit_batch_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0, la,
-                                      db, eb, x);
-            else
-                hipExtLaunchKernelGGL(geo_render_disk_emit_batch_kernel<KIND>, grid, block, 0, w.p.s, start, stop, 0,
-                                      la, db, eb);
-        });
+        if (w.ss) return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_emit_batch_kernel<KIND>, db, eb, x);
+        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_emit_batch_kernel<KIND>, db, eb);
     });
 }
 

@@ -653,11 +653,13 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
 }
 
 // ---- GEO_FLAG_DISK: the thin accretion disk (geo_disk.h) ----------------
-// The disk render's own kernel, so that geo_render_kernel's instantiations
-// carry no new branch, argument or register: GEO_MODE_DIRECT, level-0
-// sampler, one frame, one wave per workgroup on the 1-D grid of the plain
+// The disk renders are kernels of their own beside geo_render_kernel, whose
+// instantiations carry no disk branch, argument or register: GEO_MODE_DIRECT,
+// level-0 sampler, one wave per workgroup on the 1-D grid of the plain
 // direct-mode render (wave_blocks), the same tile mapping, step counting and
-// tile-cost recording.
+// tile-cost recording.  The argument structs come first, then the ring
+// kernels, then the one body of all the others (wave_block_body) and its
+// __global__ wrappers.
 struct DiskArgs {
     geo::DiskConsts k;
     const uint32_t* tex;  // padded (geo::pad_sky): (tex_w + 2) x (tex_h + 2) texels
@@ -666,158 +668,18 @@ struct DiskArgs {
     float* out_hits;  // optional: 3 x (r, U) per pixel
 };
 
-// The one-frame disk kernels' epilogue, geo_render_kernel's step counting and
-// tile-cost recording (every lane of the wave is active again here, as there):
-// the wave's steps into its sharded slot and, where the launch records costs,
-// its largest step count into its tile's.  (The batch kernel and
-// geo_render_kernel keep their own copies: through this helper their code came
-// out different)
-__device__ __forceinline__ void disk_wave_epilogue(const RenderArgs& a, uint2 tile, uint32_t tiles_x, uint32_t wave,
-                                                   uint32_t lane, uint32_t steps) {
-    if (a.step_slots) {
-        const uint32_t total = wave_sum_u32(steps);
-        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
-        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
-    }
-    if (a.tile_cost) {
-        const uint32_t wmax = wave_max_u32(steps);
-        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                             const DiskArgs d) {
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z;
-        geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                               &c2x, &c2y, &c2z);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        geo::DiskRay dr;
-        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
-                                                                    kBufferRsrcWord3),
-                                  d.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-        };
-        a.out_rgba[o] = geo::disk_shade(d.k, a.k, dr, Uk, steps, ang, base, dsample,
-                                        d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr);
-        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
-        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
-        if (a.out_steps) a.out_steps[o] = steps;
-    }
-    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
-}
-
-// The shifted render (geo_set_disk_shift): the kernel above with the ray's
-// shift terms computed once per lane and the per-hit ones in the hit arm of
-// geo::disk_shade_shift_slot_; the RK4 loop is the plain render's.  A kernel
-// of its own with a further argument, not a parameter of the one above: that
-// one's code, argument segment and resource records stay as they were (a
-// shared inlined body changed its instruction schedule).  The two bodies are
-// kept in step by the CPU path, which has one (run_rows_disk, cpu_render.cpp):
-// both kernels are tested against it bit for bit.
+// The shifted render (geo_set_disk_shift): the ray's shift terms are computed
+// once per lane and the per-hit ones in the hit arm of
+// geo::disk_shade_shift_slot_; the RK4 loop is the plain render's.
 struct DiskShiftArgs {
     geo::DiskShift k;
     float* out_g;  // optional: 3 x g per pixel
 };
 
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                   const DiskArgs d, const DiskShiftArgs sh) {
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z, g_obs;
-        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                                 &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        geo::DiskRay dr;
-        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
-                                                                    kBufferRsrcWord3),
-                                  d.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-        };
-        geo::DiskShiftRay sr;
-        geo::disk_shift_ray(d.k, sh.k, dr, ct, g_obs, &sr);
-        a.out_rgba[o] = geo::disk_shade_shift(d.k, a.k, dr, sh.k, sr, Uk, steps, ang, base, dsample,
-                                              d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr,
-                                              sh.out_g ? sh.out_g + o * geo::kDiskMaxCrossings : nullptr);
-        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
-        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
-        if (a.out_steps) a.out_steps[o] = steps;
-    }
-    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
-}
-
-// The emission render (geo_set_disk_emission): the shifted kernel's prologue,
-// loop and epilogue with geo::disk_shade_emit_slot_'s hit arm, which turns g
-// and r into q = T_obs / t_ref, reads the ramp's two neighbouring entries (two
-// dword loads, inside the arm only) and scales the texture sample.  A kernel
-// of its own with its own further argument, for the reason given above.
+// The emission render (geo_set_disk_emission): the shifted render with
+// geo::disk_shade_emit_slot_'s hit arm, which turns g and r into
+// q = T_obs / t_ref, reads the ramp's two neighbouring entries (two dword
+// loads, inside the arm only) and scales the texture sample.
 struct DiskEmitArgs {
     geo::DiskEmission k;
     const uint32_t* ramp;  // k.n2 + 2 RGBA8 entries
@@ -825,73 +687,15 @@ struct DiskEmitArgs {
     float* out_q;          // optional: 3 x q per pixel
 };
 
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                  const DiskArgs d, const DiskEmitArgs em) {
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z, g_obs;
-        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                                 &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        geo::DiskRay dr;
-        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
-                                                                    kBufferRsrcWord3),
-                                  d.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-        };
-        const auto rfetch = [ramp = em.ramp](uint32_t i) { return ramp[i]; };
-        geo::DiskShiftRay sr;
-        geo::disk_shift_ray(d.k, em.k.s, dr, ct, g_obs, &sr);
-        a.out_rgba[o] = geo::disk_shade_emit(d.k, a.k, dr, em.k, sr, Uk, steps, ang, base, dsample, rfetch,
-                                             d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr,
-                                             em.out_g ? em.out_g + o * geo::kDiskMaxCrossings : nullptr,
-                                             em.out_q ? em.out_q + o * geo::kDiskMaxCrossings : nullptr);
-        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
-        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
-        if (a.out_steps) a.out_steps[o] = steps;
-    }
-    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
-}
 
 // ---- geo_set_disk_ring_f64: the disk's capture band in f64 ----------------
-// The three one-frame disk kernels above (VAR: unshaded, shifted, emission)
+// The three one-frame disk renders (VAR: unshaded, shifted, emission)
 // with the band's lanes (geo::in_band on the f32 ray, GEO_FLAG_RING_F64's
 // test) taken through the f64 path of geo_band.h, probes included
-// (geo::disk_hits_band).  Kernels of their own on the same launch geometry:
-// the kernels above keep their code and records.  As in
+// (geo::disk_hits_band).  Kernels with their own body on the same launch
+// geometry, not a property of wave_block_body below: their lanes go through
+// geo::DiskHits and geo::disk_shade_hits, which the three geo::disk_shade*
+// forms are not yet expressed through.  As in
 // geo_render_kernel<..., RING>, the band's constants are a kernel argument
 // copied to LDS, a wave's f32 lanes run their loop (geo::geodesic_angle_disk)
 // first and its band lanes, if it has any, the f64 loop in a cold arm, and a
@@ -1015,7 +819,7 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
         if (a.out_uv) a.out_uv[o] = make_float2(U, V);
         if (a.out_steps) a.out_steps[o] = steps;
     }
-    // disk_wave_epilogue with the ring kernel's tile cost: the wave runs its
+    // wave_block_body's epilogue with the ring kernel's tile cost: the wave runs its
     // f32 lanes' loop, then its band lanes' f64 loop at about twice the cost
     // per step (every lane of the wave is active again here)
     if (a.step_slots) {
@@ -1030,8 +834,9 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
 }
 
 // ---- geo_render_disk_batch: up to kMaxBatchFrames disk frames in one launch --
-// The two kernels above with the frame in blockIdx.z (its output a.out_frame_px
-// pixels after the last frame's), colour only, on the same wave-block grid.
+// The plain and the shifted disk render with the frame in blockIdx.z (its output
+// a.out_frame_px pixels after the last frame's), colour only, on the same
+// wave-block grid.
 // RenderArgs and FrameBatch<kMaxBatchFrames> leave no room in the 4 KiB of
 // kernel arguments for eight frames' disk constants, so the batch has a
 // per-frame struct of its own: FrameK without what no disk kernel reads
@@ -1067,108 +872,15 @@ struct DiskBatchArgs {
 // 1-D wave-block grid, with the frame in grid.z.  The plain batch's 32 x 8-pixel
 // workgroups of four waves on a 2-D grid were measured against it.
 
-// SHIFT: the shaded batch (geo_set_disk_shift).  One template: no kernel that
-// existed before shares a body with it.
-template <int KIND, bool SHIFT>
-__global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderArgs a, const DiskBatchArgs db) {
-    const uint32_t z = blockIdx.z;
-    const DiskFrameK& f = db.f[z];
-    const size_t obase = (size_t)z * a.out_frame_px;
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z, g_obs = 0.0f;
-        if constexpr (SHIFT)
-            geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
-        else
-            geo::pixel_central_dir(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
-        geo::DiskConsts dk;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            dk.N[i] = f.N[i];
-            dk.ex[i] = f.ex[i];
-            dk.ey[i] = f.ey[i];
-        }
-        dk.r_in = db.r_in;
-        dk.r_out = db.r_out;
-        dk.inv_dr = db.inv_dr;
-        dk.u_lo = f.u_lo;
-        dk.u_hi = f.u_hi;
-        dk.inv_step = db.inv_step;
-        const geo::PixelConsts& k = f.k;
-        geo::DiskRay dr;
-        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = obase + (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
-                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
-                                  db.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
-        };
-        if constexpr (SHIFT) {
-            geo::DiskShift sk;
-            sk.sb = f.sb;
-            sk.ih = f.ih;
-            sk.gain = db.gain;
-            sk.exponent = db.exponent;
-            geo::DiskShiftRay sr;
-            geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
-            a.out_rgba[o] = geo::disk_shade_shift(dk, k, dr, sk, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
-        } else {
-            a.out_rgba[o] = geo::disk_shade(dk, k, dr, Uk, steps, ang, base, dsample, nullptr);
-        }
-    }
-    // (every lane of the wave is active again here, as in geo_render_kernel)
-    if (a.step_slots) {
-        const uint32_t total = wave_sum_u32(steps);
-        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
-        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
-    }
-    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
-        const uint32_t wmax = wave_max_u32(steps);
-        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
-    }
-}
-
 // ---- GEO_FLAG_SS4: 2 x 2 supersampling, resolved in the kernel -----------
-// The one-frame direct-mode kernels above with a lane per SAMPLE: RenderArgs
+// The one-frame direct-mode renders with a lane per SAMPLE: RenderArgs
 // describes the sample frame (width, height, row0, nrows, band_rows and
 // band_stride are twice the call's; f.cam is geo::camera_consts at twice the
 // size), so a lane traces and shades pixel (px, py) of the 2W x 2H render
 // exactly as its one-sample sibling does, keeps the colour in a register, and
 // the wave's 16 x 4 samples are resolved to 8 x 2 output pixels across its
-// lanes.  Kernels of their own (VAR: the plain frame, the disk frame, the
-// shifted disk frame) with their own further argument: the kernels that
-// existed before keep their code, arguments and resource records.
+// lanes.  VAR: the plain frame, the disk frame, the shifted disk frame, each
+// with its own further argument.
 constexpr int kSsPlain = 0, kSsDisk = 1, kSsDiskShift = 2;
 template <int VAR>
 struct SsArgs {
@@ -1213,167 +925,12 @@ __device__ __forceinline__ uint32_t ss_resolve(uint32_t c) {
     return rb | (ga << 8);
 }
 
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                           const SsArgs<VAR> x) {
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    // (px, ly): the lane's sample in the 2W x 2 nrows grid; py its row of the
-    // 2H sample frame.  The band index is taken on output rows (wl0 / 2 over
-    // the call's band_rows: band_magic is that divisor's, within the range
-    // band_rows_magic is exact on); a.band_rows, a.band_stride and a.row0 are
-    // in sample rows.  Bands are multiples of 16 sample rows, so the wave's
-    // four rows lie in one.
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    // In the frame or out of it, the four samples of an output pixel go
-    // together: a.width, a.nrows and a.height are even (twice the call's),
-    // px and px ^ 1 differ in bit 0 only, and so do ly and ly ^ 1 and, with
-    // them, py and its partner (wl0 is a multiple of 4; a.row0, a.band_stride
-    // and a.band_rows are even, so py - (ly - wl0) is even and py's bit 0 is
-    // ly's).  Lanes l ^ 1 and l ^ 16 hold samples (px ^ 1, ly) and (px, ly ^ 1).
-    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
-    uint32_t steps = 0;
-    uint32_t colour = 0;  // the sample's colour, kept in a register
-    if (in_frame) {
-        float c2x, c2y, c2z, g_obs = 0.0f;
-        if constexpr (VAR == kSsDiskShift)
-            geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px,
-                                     py, &c2x, &c2y, &c2z, &g_obs);
-        else
-            geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                                   &c2x, &c2y, &c2z);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        if constexpr (VAR == kSsPlain) {
-            const float lam = pixel_lambda<GEO_MODE_DIRECT, KIND>(a, a.k, st, ct, rct, &steps);
-            const bool bh = lam < geo::kBlackHoleLambda;
-            float U = 0.0f, V = 0.0f;
-            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-            colour = bh ? geo::kBlackRGBA
-                        : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        } else {
-            const DiskArgs& d = x.d;
-            geo::DiskRay dr;
-            geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
-            float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-            const float lam = geo::kPi2 - ang;
-            const bool bh = lam < geo::kBlackHoleLambda;
-            float U = 0.0f, V = 0.0f;
-            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-            const uint32_t base = bh ? geo::kBlackRGBA
-                                     : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-            const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0,
-                                                                        (int)d.tex_bytes, kBufferRsrcWord3),
-                                      d.tex_pitch_b};
-            const auto dsample = [&](float Ud, float Vd) {
-                return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-            };
-            if constexpr (VAR == kSsDiskShift) {
-                geo::DiskShiftRay sr;
-                geo::disk_shift_ray(d.k, x.sh.k, dr, ct, g_obs, &sr);
-                colour = geo::disk_shade_shift(d.k, a.k, dr, x.sh.k, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
-            } else {
-                colour = geo::disk_shade(d.k, a.k, dr, Uk, steps, ang, base, dsample, nullptr);
-            }
-        }
-    }
-    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
-    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
-    // of the frame resolves four zeros and is not stored.
-    const uint32_t resolved = ss_resolve(colour);
-    if (in_frame && (lane & 0x11u) == 0u) a.out_rgba[(size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
-    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
-}
-
-// The supersampled emission frame (geo_set_disk_emission with GEO_FLAG_SS4):
-// geo_render_ss_kernel's disk arm with geo::disk_shade_emit.  A kernel of its
-// own, not a fourth VAR of the template above: that template's body, and with
-// it the code of its nine instantiations, stays untouched.
+// The supersampled emission frame (geo_set_disk_emission with GEO_FLAG_SS4).
 struct SsEmitArgs {
     uint32_t out_width;
     DiskArgs d;
     DiskEmitArgs em;
 };
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_ss_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                const SsEmitArgs x) {
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    // (the sample grid, the band index and the quad partners: geo_render_ss_kernel's)
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
-    uint32_t steps = 0;
-    uint32_t colour = 0;  // the sample's colour, kept in a register
-    if (in_frame) {
-        float c2x, c2y, c2z, g_obs;
-        geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                                 &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        const DiskArgs& d = x.d;
-        geo::DiskRay dr;
-        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
-                                                                    kBufferRsrcWord3),
-                                  d.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-        };
-        const auto rfetch = [ramp = x.em.ramp](uint32_t i) { return ramp[i]; };
-        geo::DiskShiftRay sr;
-        geo::disk_shift_ray(d.k, x.em.k.s, dr, ct, g_obs, &sr);
-        colour = geo::disk_shade_emit(d.k, a.k, dr, x.em.k, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
-                                      nullptr);
-    }
-    // (all 64 lanes are active again, as the exchange needs)
-    const uint32_t resolved = ss_resolve(colour);
-    if (in_frame && (lane & 0x11u) == 0u) a.out_rgba[(size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
-    disk_wave_epilogue(a, tile, tiles_x, wave, lane, steps);
-}
 
 // ---- geo_render_ss_batch: up to kMaxBatchFrames GEO_FLAG_SS4 frames in one launch --
 // geo_render_ss_kernel with the frame in blockIdx.z, on the disk batch's
@@ -1381,8 +938,8 @@ __global__ __launch_bounds__(64) void geo_render_ss_emit_kernel(const RenderArgs
 // Frame z's constants come from the batched kernels' own argument structs,
 // indexed by z (uniform: scalar loads): the plain variant reads
 // FrameBatch<kMaxBatchFrames> (f[z], k[z]), the disk variants DiskBatchArgs
-// (DiskFrameK, assembled into geo::DiskConsts and geo::DiskShift as
-// geo_render_disk_batch_kernel does).  The host fills both with the one-frame
+// (DiskFrameK, assembled into geo::DiskConsts and geo::DiskShift by
+// DiskBatchFrame below).  The host fills both with the one-frame
 // SS launch's functions at the sample frame's size, so a batch frame is its
 // one-frame render bit for bit.  The output's pitch rides in SsBatchOut; frame
 // z's output starts a.out_frame_px output pixels after frame z - 1's.
@@ -1398,128 +955,10 @@ struct SsBatchFrames<kSsPlain> {
     using type = FrameBatch<kMaxBatchFrames>;
 };
 
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) void geo_render_ss_batch_kernel(const RenderArgs a,
-                                                                 const typename SsBatchFrames<VAR>::type fb,
-                                                                 const SsBatchOut x) {
-    const uint32_t z = blockIdx.z;
-    const auto& f = fb.f[z];
-    const size_t obase = (size_t)z * a.out_frame_px;
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    // the only early exit, and a wave-uniform one: ss_resolve below needs every lane
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    // the sample grid, the band mapping on output rows and the quads' parity:
-    // geo_render_ss_kernel's, which see
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
-    uint32_t steps = 0;
-    uint32_t colour = 0;  // the sample's colour, kept in a register
-    if (in_frame) {
-        if constexpr (VAR == kSsPlain) {
-            float c2x, c2y, c2z;
-            geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px, py,
-                                   &c2x, &c2y, &c2z);
-            const float st = geo::central_sin(c2z);
-            const float ct = geo::central_rho(c2x, c2y);
-            const float rct = geo::rcpf_(ct);
-            const float lam = pixel_lambda<GEO_MODE_DIRECT, KIND>(a, fb.k[z], st, ct, rct, &steps);
-            const bool bh = lam < geo::kBlackHoleLambda;
-            float U = 0.0f, V = 0.0f;
-            if (!bh) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-            colour = bh ? geo::kBlackRGBA
-                        : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        } else {
-            float c2x, c2y, c2z, g_obs = 0.0f;
-            if constexpr (VAR == kSsDiskShift)
-                geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
-            else
-                geo::pixel_central_dir(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z);
-            const float st = geo::central_sin(c2z);
-            const float ct = geo::central_rho(c2x, c2y);
-            const float rct = geo::rcpf_(ct);
-            // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
-            geo::DiskConsts dk;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                dk.N[i] = f.N[i];
-                dk.ex[i] = f.ex[i];
-                dk.ey[i] = f.ey[i];
-            }
-            dk.r_in = fb.r_in;
-            dk.r_out = fb.r_out;
-            dk.inv_dr = fb.inv_dr;
-            dk.u_lo = f.u_lo;
-            dk.u_hi = f.u_hi;
-            dk.inv_step = fb.inv_step;
-            const geo::PixelConsts& k = f.k;
-            geo::DiskRay dr;
-            geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
-            float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
-            const float lam = geo::kPi2 - ang;
-            const bool bh = lam < geo::kBlackHoleLambda;
-            float U = 0.0f, V = 0.0f;
-            if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-            const uint32_t base = bh ? geo::kBlackRGBA
-                                     : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-            const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(fb.tex), 0,
-                                                                        (int)fb.tex_bytes, kBufferRsrcWord3),
-                                      fb.tex_pitch_b};
-            const auto dsample = [&](float Ud, float Vd) {
-                return geo::sample_sky_quad_f(dquad, fb.tex_w256, fb.tex_h256, Ud, Vd);
-            };
-            if constexpr (VAR == kSsDiskShift) {
-                geo::DiskShift sk;
-                sk.sb = f.sb;
-                sk.ih = f.ih;
-                sk.gain = fb.gain;
-                sk.exponent = fb.exponent;
-                geo::DiskShiftRay sr;
-                geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
-                colour = geo::disk_shade_shift(dk, k, dr, sk, sr, Uk, steps, ang, base, dsample, nullptr, nullptr);
-            } else {
-                colour = geo::disk_shade(dk, k, dr, Uk, steps, ang, base, dsample, nullptr);
-            }
-        }
-    }
-    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
-    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
-    // of the frame resolves four zeros and is not stored.
-    const uint32_t resolved = ss_resolve(colour);
-    if (in_frame && (lane & 0x11u) == 0u)
-        a.out_rgba[obase + (size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
-    if (a.step_slots) {
-        const uint32_t total = wave_sum_u32(steps);
-        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
-        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
-    }
-    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
-        const uint32_t wmax = wave_max_u32(steps);
-        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
-    }
-}
-
 // ---- geo_render_emission_batch: up to kMaxBatchFrames emission frames in one launch --
-// geo_render_disk_batch_kernel's shaded body and geo_render_ss_batch_kernel's
-// disk body with geo::disk_shade_emit as the hit arm (null per-pixel outputs:
-// a batch draws colour only).  Kernels of their own, not a further template
-// parameter or VAR of those two: their code, argument segments and resource
-// records stay as they were.  DiskBatchArgs is reused unchanged: of a
+// The shaded disk batch and the SS batch's disk frames with
+// geo::disk_shade_emit as the hit arm (null per-pixel outputs: a batch draws
+// colour only).  DiskBatchArgs is reused unchanged: of a
 // geo::DiskEmission only sb and ih change with the frame (its r_obs and
 // det M2), and DiskFrameK carries them, filled by geo::disk_emission_consts
 // with the emission's spin; the batch-uniform rest and the ramp ride in one
@@ -1532,74 +971,112 @@ struct DiskEmitBatchArgs {
     const uint32_t* ramp;  // n2 + 2 RGBA8 entries
 };
 
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                        const DiskEmitBatchArgs eb) {
-    const uint32_t z = blockIdx.z;
-    const DiskFrameK& f = db.f[z];
-    const size_t obase = (size_t)z * a.out_frame_px;
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z, g_obs;
-        geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
+// ---- the one body of the disk and SS4 kernels on the wave-block grid ------
+// Every kernel below (all of this file's wave-block kernels but
+// geo_render_kernel and the ring kernels) is a wrapper that names its frame
+// source and calls wave_block_body, which holds what they share: the tile
+// mapping, the camera ray, geo::disk_ray and geo::geodesic_angle_disk, the sky
+// sample, the disk texture quad, the shading call, the SS4 resolve, and the
+// step-slot and tile-cost epilogue.  It varies along four properties of the
+// render, not of the caller:
+//   SHADE  what is shaded: the sky alone (pixel_lambda), or the disk plain,
+//          shifted or with its emission (geo::disk_shade, _shift, _emit)
+//   SS     one sample per pixel, or GEO_FLAG_SS4: a lane per sample, the band
+//          index on output rows, the colour kept in a register, ss_resolve
+//          and one store per 2 x 2 quad
+//   SIDE   the per-pixel side outputs of the one-frame one-sample renders
+//          (mask, uv, steps, hits, g, q; the sky UV also where only a.out_uv
+//          asks for it); every other render is colour only
+//   SRC    the frame source: what frame z of the launch reads its camera,
+//          scene, disk, texture, shift or emission constants and ramp from,
+//          where its output starts and whether it records tile costs, one
+//          struct per argument layout (SkyFrame<1>, SkyFrame<kMaxBatchFrames>,
+//          DiskFrame, DiskBatchFrame)
+// A new variant is a new value of a property and a wrapper, not a copy of the
+// body.  One body on the CPU path too (run_rows_disk, cpu_render.cpp), which
+// every wrapper is tested against bit for bit.
+enum class Shade { kSky, kDisk, kDiskShift, kDiskEmit };
+struct NoArgs {};
+
+// FrameBatch<NF> and the scene constants of frame_consts: the sky-only renders
+// (and, as DiskFrame's base, the one-frame disk renders).
+template <uint32_t NF>
+struct SkyFrame {
+    const RenderArgs& a;
+    const FrameBatch<NF>& fb;
+    uint32_t z;  // the frame of the launch (0 of one)
+    __device__ __forceinline__ const FrameK& f() const { return fb.f[NF > 1 ? z : 0u]; }
+    __device__ __forceinline__ const geo::CameraConsts& cam() const { return f().cam; }
+    __device__ __forceinline__ const float* movement_to_central() const { return f().frame.movement_to_central; }
+    __device__ __forceinline__ const float* central_to_uv() const { return f().frame.central_to_uv; }
+    __device__ __forceinline__ float psi() const { return f().frame.psi_factor_and_position[0]; }
+    __device__ __forceinline__ float kt() const { return f().kt; }
+    __device__ __forceinline__ const geo::PixelConsts& consts() const { return frame_consts(a, fb, z); }
+    __device__ __forceinline__ size_t out_base() const { return NF > 1 ? (size_t)z * a.out_frame_px : 0; }
+    // (frame 0's of a batch: the order is per tile)
+    __device__ __forceinline__ bool records_cost() const { return NF == 1 || z == 0u; }
+};
+
+// FrameBatch<1>, RenderArgs::k and DiskArgs, with the shaded renders' further
+// argument X (DiskShiftArgs or DiskEmitArgs): the constants by reference.
+template <typename X>
+struct DiskFrame : SkyFrame<1> {
+    const DiskArgs& d;
+    const X& x;
+    __device__ __forceinline__ const geo::DiskConsts& disk() const { return d.k; }
+    __device__ __forceinline__ const DiskArgs& tex() const { return d; }
+    __device__ __forceinline__ const geo::DiskShift& shift() const { return x.k; }
+    __device__ __forceinline__ const geo::DiskEmission& emission() const { return x.k; }
+    __device__ __forceinline__ const uint32_t* ramp() const { return x.ramp; }
+};
+
+// DiskBatchArgs, with the emission batch's further argument E: frame z's
+// geo::DiskConsts, geo::DiskShift and geo::DiskEmission assembled by value
+// from its DiskFrameK and the batch's part (wave-uniform: they stay scalars).
+template <typename E>
+struct DiskBatchFrame {
+    const RenderArgs& a;
+    const DiskBatchArgs& db;
+    const E& eb;
+    uint32_t z;
+    __device__ __forceinline__ const DiskFrameK& f() const { return db.f[z]; }
+    __device__ __forceinline__ const geo::CameraConsts& cam() const { return f().cam; }
+    __device__ __forceinline__ const float* movement_to_central() const { return f().movement_to_central; }
+    __device__ __forceinline__ const float* central_to_uv() const { return f().central_to_uv; }
+    __device__ __forceinline__ float psi() const { return f().psi; }
+    __device__ __forceinline__ float kt() const { return f().kt; }
+    __device__ __forceinline__ const geo::PixelConsts& consts() const { return f().k; }
+    __device__ __forceinline__ size_t out_base() const { return (size_t)z * a.out_frame_px; }
+    __device__ __forceinline__ bool records_cost() const { return z == 0u; }  // frame 0's: the order is per tile
+    __device__ __forceinline__ geo::DiskConsts disk() const {
         geo::DiskConsts dk;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            dk.N[i] = f.N[i];
-            dk.ex[i] = f.ex[i];
-            dk.ey[i] = f.ey[i];
+            dk.N[i] = f().N[i];
+            dk.ex[i] = f().ex[i];
+            dk.ey[i] = f().ey[i];
         }
         dk.r_in = db.r_in;
         dk.r_out = db.r_out;
         dk.inv_dr = db.inv_dr;
-        dk.u_lo = f.u_lo;
-        dk.u_hi = f.u_hi;
+        dk.u_lo = f().u_lo;
+        dk.u_hi = f().u_hi;
         dk.inv_step = db.inv_step;
-        const geo::PixelConsts& k = f.k;
-        geo::DiskRay dr;
-        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = obase + (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
-                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
-                                  db.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
-        };
-        const auto rfetch = [ramp = eb.ramp](uint32_t i) { return ramp[i]; };
-        // frame z's geo::DiskEmission (its gain and exponent are not read)
+        return dk;
+    }
+    __device__ __forceinline__ const DiskBatchArgs& tex() const { return db; }
+    __device__ __forceinline__ geo::DiskShift shift() const {
+        geo::DiskShift sk;
+        sk.sb = f().sb;
+        sk.ih = f().ih;
+        sk.gain = db.gain;
+        sk.exponent = db.exponent;
+        return sk;
+    }
+    __device__ __forceinline__ geo::DiskEmission emission() const {  // (its gain and exponent are not read)
         geo::DiskEmission ek;
-        ek.s.sb = f.sb;
-        ek.s.ih = f.ih;
+        ek.s.sb = f().sb;
+        ek.s.ih = f().ih;
         ek.s.gain = 1.0f;
         ek.s.exponent = 0u;
         ek.inv_fmax = eb.inv_fmax;
@@ -1609,127 +1086,221 @@ __global__ __launch_bounds__(64) void geo_render_disk_emit_batch_kernel(const Re
         ek.exposure = eb.exposure;
         ek.profile = eb.profile;
         ek.n2 = eb.n2;
-        geo::DiskShiftRay sr;
-        geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
-        a.out_rgba[o] = geo::disk_shade_emit(dk, k, dr, ek, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
-                                             nullptr);
+        return ek;
     }
-    // (every lane of the wave is active again here, as in geo_render_kernel)
+    __device__ __forceinline__ const uint32_t* ramp() const { return eb.ramp; }
+};
+
+// out_width (SS): the output's pitch in pixels; RenderArgs then describes the
+// sample frame.
+template <int KIND, Shade SHADE, bool SS, bool SIDE, typename SRC>
+__device__ __forceinline__ void wave_block_body(const RenderArgs& a, const SRC& src, uint32_t out_width) {
+    static_assert(!(SS && SIDE) && !(SIDE && SHADE == Shade::kSky), "side outputs: the one-sample disk renders'");
+    // geo_render_kernel's WB mapping: workgroup L draws wave `wave` of the tile
+    // at dispatch position pos.  The padding of the last group (a whole
+    // workgroup) leaves here: the body's only early exit, and a wave-uniform
+    // one, because ss_resolve below needs every lane of the wave.
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // SS: (px, ly) is the lane's sample in the 2W x 2 nrows grid; py its row of
+    // the 2H sample frame.  The band index is taken on output rows (wl0 / 2
+    // over the call's band_rows: band_magic is that divisor's, within the range
+    // band_rows_magic is exact on); a.band_rows, a.band_stride and a.row0 are
+    // in sample rows.  Bands are multiples of 16 sample rows, so the wave's
+    // four rows lie in one.
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(SS ? wl0 >> 1 : wl0, a.band_magic);
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    // SS: in the frame or out of it, the four samples of an output pixel go
+    // together: a.width, a.nrows and a.height are even (twice the call's),
+    // px and px ^ 1 differ in bit 0 only, and so do ly and ly ^ 1 and, with
+    // them, py and its partner (wl0 is a multiple of 4; a.row0, a.band_stride
+    // and a.band_rows are even, so py - (ly - wl0) is even and py's bit 0 is
+    // ly's).  Lanes l ^ 1 and l ^ 16 hold samples (px ^ 1, ly) and (px, ly ^ 1).
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // SS: the sample's colour, kept in a register
+    if (in_frame) {
+        float c2x, c2y, c2z, g_obs = 0.0f;
+        if constexpr (SHADE == Shade::kDiskShift || SHADE == Shade::kDiskEmit)
+            geo::pixel_central_dir_g(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y,
+                                     &c2z, &g_obs);
+        else
+            geo::pixel_central_dir(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y, &c2z);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        const geo::PixelConsts& k = src.consts();
+        const size_t o = src.out_base() + (size_t)ly * a.width + px;  // (one sample per pixel)
+        if constexpr (SHADE == Shade::kSky) {
+            const float lam = pixel_lambda<GEO_MODE_DIRECT, KIND>(a, k, st, ct, rct, &steps);
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh) geo::sky_uv(src.central_to_uv(), c2x, c2y, ct, rct, lam, &U, &V);
+            colour = bh ? geo::kBlackRGBA
+                        : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+            if constexpr (!SS) a.out_rgba[o] = colour;
+        } else {
+            const auto& dk = src.disk();
+            geo::DiskRay dr;
+            geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+            float Uk[geo::kDiskMaxCrossings];
+            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            const float lam = geo::kPi2 - ang;
+            const bool bh = lam < geo::kBlackHoleLambda;
+            float U = 0.0f, V = 0.0f;
+            if (!bh || (SIDE && a.out_uv)) geo::sky_uv(src.central_to_uv(), c2x, c2y, ct, rct, lam, &U, &V);
+            const uint32_t base =
+                bh ? geo::kBlackRGBA
+                   : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+            const auto& t = src.tex();
+            const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(t.tex), 0,
+                                                                        (int)t.tex_bytes, kBufferRsrcWord3),
+                                      t.tex_pitch_b};
+            const auto dsample = [&](float Ud, float Vd) {
+                return geo::sample_sky_quad_f(dquad, t.tex_w256, t.tex_h256, Ud, Vd);
+            };
+            float *hits = nullptr, *gs = nullptr, *qs = nullptr;
+            if constexpr (SIDE) {
+                hits = src.d.out_hits ? src.d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
+                if constexpr (SHADE != Shade::kDisk)
+                    gs = src.x.out_g ? src.x.out_g + o * geo::kDiskMaxCrossings : nullptr;
+                if constexpr (SHADE == Shade::kDiskEmit)
+                    qs = src.x.out_q ? src.x.out_q + o * geo::kDiskMaxCrossings : nullptr;
+            }
+            if constexpr (SHADE == Shade::kDiskEmit) {
+                const auto rfetch = [ramp = src.ramp()](uint32_t i) { return ramp[i]; };
+                const auto& ek = src.emission();
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
+                colour = geo::disk_shade_emit(dk, k, dr, ek, sr, Uk, steps, ang, base, dsample, rfetch, hits, gs, qs);
+            } else if constexpr (SHADE == Shade::kDiskShift) {
+                const auto& sk = src.shift();
+                geo::DiskShiftRay sr;
+                geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
+                colour = geo::disk_shade_shift(dk, k, dr, sk, sr, Uk, steps, ang, base, dsample, hits, gs);
+            } else {
+                colour = geo::disk_shade(dk, k, dr, Uk, steps, ang, base, dsample, hits);
+            }
+            if constexpr (!SS) a.out_rgba[o] = colour;
+            if constexpr (SIDE) {
+                if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
+                if (a.out_uv) a.out_uv[o] = make_float2(U, V);
+                if (a.out_steps) a.out_steps[o] = steps;
+            }
+        }
+    }
+    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
+    // rejoined: all 64 lanes are active, as the resolve's exchange and the
+    // wave reductions need.
+    if constexpr (SS) {
+        // a pixel out of the frame resolves four zeros and is not stored
+        const uint32_t resolved = ss_resolve(colour);
+        if (in_frame && (lane & 0x11u) == 0u)
+            a.out_rgba[src.out_base() + (size_t)(ly >> 1) * out_width + (px >> 1)] = resolved;
+    }
+    // geo_render_kernel's step counting and tile-cost recording: the wave's
+    // steps into its sharded slot and, where the launch records costs, its
+    // largest step count into its tile's
     if (a.step_slots) {
         const uint32_t total = wave_sum_u32(steps);
         const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
         if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
     }
-    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
+    if (a.tile_cost && src.records_cost()) {
         const uint32_t wmax = wave_max_u32(steps);
         if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
     }
 }
 
-// The same with GEO_FLAG_SS4: a lane per sample of the 2W x 2H frame, resolved
-// across the wave's lanes (geo_render_ss_batch_kernel's sample grid, band
-// mapping on output rows and quad parity, which see).
+// The one-frame disk renders: plain, shifted (geo_set_disk_shift), emission
+// (geo_set_disk_emission).
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                             const DiskArgs d) {
+    wave_block_body<KIND, Shade::kDisk, false, true>(a, DiskFrame<NoArgs>{{a, fb, 0u}, d, NoArgs{}}, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                   const DiskArgs d, const DiskShiftArgs sh) {
+    wave_block_body<KIND, Shade::kDiskShift, false, true>(a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, d, sh}, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                  const DiskArgs d, const DiskEmitArgs em) {
+    wave_block_body<KIND, Shade::kDiskEmit, false, true>(a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, d, em}, 0u);
+}
+
+// geo_render_disk_batch.  SHIFT: the shaded batch (geo_set_disk_shift).
+template <int KIND, bool SHIFT>
+__global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderArgs a, const DiskBatchArgs db) {
+    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, false, false>(
+        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, 0u);
+}
+
+// GEO_FLAG_SS4, one frame.
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                           const SsArgs<VAR> x) {
+    if constexpr (VAR == kSsPlain)
+        wave_block_body<KIND, Shade::kSky, true, false>(a, SkyFrame<1>{a, fb, 0u}, x.out_width);
+    else if constexpr (VAR == kSsDisk)
+        wave_block_body<KIND, Shade::kDisk, true, false>(a, DiskFrame<NoArgs>{{a, fb, 0u}, x.d, NoArgs{}}, x.out_width);
+    else
+        wave_block_body<KIND, Shade::kDiskShift, true, false>(a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, x.d, x.sh},
+                                                              x.out_width);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_ss_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                const SsEmitArgs x) {
+    wave_block_body<KIND, Shade::kDiskEmit, true, false>(a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, x.d, x.em},
+                                                         x.out_width);
+}
+
+// geo_render_ss_batch.
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) void geo_render_ss_batch_kernel(const RenderArgs a,
+                                                                 const typename SsBatchFrames<VAR>::type fb,
+                                                                 const SsBatchOut x) {
+    if constexpr (VAR == kSsPlain)
+        wave_block_body<KIND, Shade::kSky, true, false>(a, SkyFrame<kMaxBatchFrames>{a, fb, blockIdx.z}, x.out_width);
+    else
+        wave_block_body<KIND, VAR == kSsDiskShift ? Shade::kDiskShift : Shade::kDisk, true, false>(
+            a, DiskBatchFrame<NoArgs>{a, fb, NoArgs{}, blockIdx.z}, x.out_width);
+}
+
+// geo_render_emission_batch, and the same with GEO_FLAG_SS4.
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                        const DiskEmitBatchArgs eb) {
+    wave_block_body<KIND, Shade::kDiskEmit, false, false>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z},
+                                                          0u);
+}
+
 template <int KIND>
 __global__ __launch_bounds__(64) void geo_render_ss_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
                                                                       const DiskEmitBatchArgs eb,
                                                                       const SsBatchOut x) {
-    const uint32_t z = blockIdx.z;
-    const DiskFrameK& f = db.f[z];
-    const size_t obase = (size_t)z * a.out_frame_px;
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    // the only early exit, and a wave-uniform one: ss_resolve below needs every lane
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0 >> 1, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
-    uint32_t steps = 0;
-    uint32_t colour = 0;  // the sample's colour, kept in a register
-    if (in_frame) {
-        float c2x, c2y, c2z, g_obs;
-        geo::pixel_central_dir_g(f.cam, f.movement_to_central, f.psi, f.kt, px, py, &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        // frame z's geo::DiskConsts, from its own part and the batch's (scalars)
-        geo::DiskConsts dk;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            dk.N[i] = f.N[i];
-            dk.ex[i] = f.ex[i];
-            dk.ey[i] = f.ey[i];
-        }
-        dk.r_in = db.r_in;
-        dk.r_out = db.r_out;
-        dk.inv_dr = db.inv_dr;
-        dk.u_lo = f.u_lo;
-        dk.u_hi = f.u_hi;
-        dk.inv_step = db.inv_step;
-        const geo::PixelConsts& k = f.k;
-        geo::DiskRay dr;
-        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
-        float Uk[geo::kDiskMaxCrossings];
-        const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
-        const float lam = geo::kPi2 - ang;
-        const bool bh = lam < geo::kBlackHoleLambda;
-        float U = 0.0f, V = 0.0f;
-        if (!bh) geo::sky_uv(f.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(db.tex), 0,
-                                                                    (int)db.tex_bytes, kBufferRsrcWord3),
-                                  db.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, db.tex_w256, db.tex_h256, Ud, Vd);
-        };
-        const auto rfetch = [ramp = eb.ramp](uint32_t i) { return ramp[i]; };
-        // frame z's geo::DiskEmission (its gain and exponent are not read)
-        geo::DiskEmission ek;
-        ek.s.sb = f.sb;
-        ek.s.ih = f.ih;
-        ek.s.gain = 1.0f;
-        ek.s.exponent = 0u;
-        ek.inv_fmax = eb.inv_fmax;
-        ek.ka = eb.ka;
-        ek.kb = eb.kb;
-        ek.n1 = eb.n1;
-        ek.exposure = eb.exposure;
-        ek.profile = eb.profile;
-        ek.n2 = eb.n2;
-        geo::DiskShiftRay sr;
-        geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
-        colour = geo::disk_shade_emit(dk, k, dr, ek, sr, Uk, steps, ang, base, dsample, rfetch, nullptr, nullptr,
-                                      nullptr);
-    }
-    // Every per-lane arm (out of frame, black hole, disk hits, shading) has
-    // rejoined: all 64 lanes are active, as the exchange needs.  A pixel out
-    // of the frame resolves four zeros and is not stored.
-    const uint32_t resolved = ss_resolve(colour);
-    if (in_frame && (lane & 0x11u) == 0u)
-        a.out_rgba[obase + (size_t)(ly >> 1) * x.out_width + (px >> 1)] = resolved;
-    if (a.step_slots) {
-        const uint32_t total = wave_sum_u32(steps);
-        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
-        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
-    }
-    if (a.tile_cost && z == 0u) {  // frame 0's cost: the order is per tile
-        const uint32_t wmax = wave_max_u32(steps);
-        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
-    }
+    wave_block_body<KIND, Shade::kDiskEmit, true, false>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z},
+                                                         x.out_width);
 }
+
 
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
