@@ -63,7 +63,9 @@ extern "C" {
                                    geo_set_disk_emission, geo_disk_emission_next_render;
                                    announced by GEO_HAS_DISK_EMISSION_BATCH:
                                    geo_render_emission_batch;
-                                   announced by GEO_HAS_DISK_RING_F64: geo_set_disk_ring_f64) */
+                                   announced by GEO_HAS_DISK_RING_F64: geo_set_disk_ring_f64;
+                                   announced by GEO_HAS_DISK_RING_BATCH:
+                                   geo_render_disk_ring_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -72,6 +74,7 @@ extern "C" {
 #define GEO_HAS_DISK_EMISSION 1
 #define GEO_HAS_DISK_EMISSION_BATCH 1
 #define GEO_HAS_DISK_RING_F64 1
+#define GEO_HAS_DISK_RING_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -193,8 +196,10 @@ typedef enum geo_status {
                                    8 x 2 output pixels, resolved across its lanes
                                    (DESIGN.md §3).  Up to GEO_MAX_BATCH_FRAMES supersampled
                                    frames in one launch go through geo_render_ss_batch
-                                   (GEO_HAS_SS4_BATCH), the only batched call that takes the
-                                   flag. */
+                                   (GEO_HAS_SS4_BATCH); with the emission set through
+                                   geo_render_emission_batch, and with geo_set_disk_ring_f64
+                                   on through geo_render_disk_ring_batch, the only call
+                                   that draws a supersampled disk frame with its f64 band. */
 #define GEO_DISK_MAX_CROSSINGS 3
 #define GEO_DISK_G_MAX 16.0f    /* the largest frequency ratio a shaded hit reports
                                    (geo_set_disk_shift; csrc/geo_disk.h) */
@@ -319,7 +324,9 @@ int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
  * or batched returns GEO_EINVAL for a disk scene, launches nothing and writes
  * nothing (an armed per-pixel buffer is still consumed): GEO_FLAG_SS4 disk
  * renders, geo_render_disk_batch, geo_render_ss_batch and
- * geo_render_emission_batch (such a frame would come out without its band).
+ * geo_render_emission_batch (such a frame would come out without its band);
+ * geo_render_disk_ring_batch (GEO_HAS_DISK_RING_BATCH) draws batched and
+ * GEO_FLAG_SS4 disk frames with the band.
  * Renders without GEO_FLAG_DISK are untouched, and GEO_FLAG_DISK |
  * GEO_FLAG_RING_F64 stays GEO_EINVAL everywhere.  Off by default; kept across
  * geo_set_disk, cleared by geo_clear_disk.  GEO_EINVAL for a NULL ctx. */
@@ -610,6 +617,49 @@ int geo_render_emission_batch(geo_ctx* ctx, const geo_frame* frames, const geo_s
                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                               unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for the thin disk with its capture band in f64
+ * (GEO_HAS_DISK_RING_BATCH): nframes (1 .. GEO_MAX_BATCH_FRAMES) GEO_FLAG_DISK
+ * frames of a context with geo_set_disk_ring_f64 on, in ONE render launch,
+ * scenes[f] for frames[f], the band-set layout and the out_frame_stride rules
+ * of the other batches.  The shading is what the context has set: none,
+ * geo_set_disk_shift, or geo_set_disk_emission (which takes the shift's place,
+ * as everywhere else).
+ * One-sample frames: frame f's bytes are those of geo_render_band_set with
+ * frames[f], scenes[f] and the same context state (the ring state on), bit for
+ * bit, and so geo_render_cpu_disk_ring_f64's / _shift_ring_f64's; steps_total
+ * (or the deferred accumulator) is the sum of those renders' steps, the band's
+ * f64 steps included.
+ * GEO_FLAG_SS4 on every scene or on none (width, height, rows and bands are
+ * then in output pixels, as for geo_render_ss_batch, with its size limits).  No
+ * one-frame supersampled render exists while the state is on (it stays
+ * refused), so the flag's own definition fixes frame f: output pixel (x, y) is
+ * the per-channel (s00 + s01 + s10 + s11 + 2) >> 2 of pixels (2x + i, 2y + j)
+ * of the one-sample ring-on render at 2 width x 2 height with the same uniform
+ * and scene; the steps are those of every sample over sample rows 2r, 2r + 1.
+ * Every scene carries GEO_FLAG_DISK and GEO_MODE_DIRECT, with
+ * GEO_FLAG_DEFER_STEPS and GEO_FLAG_SS4 at most; the scenes may differ in r_obs
+ * only and share the integration kind.  geo_render_disk_batch's disk rules
+ * hold, and with a shift or an emission set so does r_in > 1.5 rs; anything
+ * else is GEO_EINVAL.  GEO_ESTATE when no sky or no disk is set, or when the
+ * ring state is off.  Colour only: a buffer armed by geo_disk_hits_next_render,
+ * geo_disk_shift_next_render or geo_disk_emission_next_render is consumed and
+ * the call returns GEO_EINVAL.  A refused call launches nothing and writes
+ * nothing; ctx, frames, scenes or out_rgba8 NULL and nframes out of range are
+ * refused before any device work.  With rs == 0 there is no capture orbit: the
+ * state is ignored and the frames are geo_render_disk_batch's, _ss_batch's or
+ * _emission_batch's.  steps_total and the deferred accumulator,
+ * geo_time_next_render (the render launch; a small kernel that writes the
+ * frames' band constants to a context-owned table runs on `stream` before it),
+ * geo_set_dispatch and geo_set_tile_order work as for the other batches (frame
+ * 0 records the tile costs, a band pixel's steps counting twice; the learned
+ * order has a grid key of its own; under GEO_FLAG_SS4 the grid is the sample
+ * frame's).  Every older call keeps every refusal it has.  One scene for every
+ * frame: pass copies.  Asynchronous on `stream`. */
+int geo_render_disk_ring_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                               unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

@@ -41,6 +41,7 @@ GEO_HAS_SS4_BATCH = 1  # geo_render_ss_batch
 GEO_HAS_DISK_EMISSION = 1  # geo_set_disk_emission, geo_disk_emission_next_render
 GEO_HAS_DISK_EMISSION_BATCH = 1  # geo_render_emission_batch
 GEO_HAS_DISK_RING_F64 = 1  # geo_set_disk_ring_f64
+GEO_HAS_DISK_RING_BATCH = 1  # geo_render_disk_ring_batch
 GEO_DISK_PROFILE_POWER = 0
 GEO_DISK_PROFILE_THIN = 1
 GEO_DISK_RAMP_MAX = 1024
@@ -175,6 +176,11 @@ SIGNATURES = {
          ctypes.c_size_t, _vp, _vp],
     ),
     "geo_render_emission_batch": (
+        _int,
+        [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
+         ctypes.c_size_t, _vp, _vp],
+    ),
+    "geo_render_disk_ring_batch": (
         _int,
         [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
          ctypes.c_size_t, _vp, _vp],

@@ -128,6 +128,13 @@ struct geo_ctx {
     // geo_set_disk_ring_f64: the disk's band lanes in f64 (kept across
     // geo_set_disk, cleared by geo_clear_disk)
     bool disk_ring;
+    // geo_render_disk_ring_batch: the frames' band constants (kMaxBatchFrames
+    // geo::BandConsts), one device table per render-stream slot, allocated at
+    // the slot's first such call.  A call writes its slot's table on its own
+    // stream just before its render launch: stream order keeps it from the
+    // stream's earlier render, and a stream that takes the slot over has
+    // waited for render_done[slot] on the host (render_slot).
+    void* band_table[kRenderStreams];
 #if defined(GEO_WAVE_LOG)
     unsigned long long* wave_log;  // diagnostic build only (geo_debug_set_wave_log)
 #endif

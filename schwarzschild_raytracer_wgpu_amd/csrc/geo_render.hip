@@ -162,6 +162,8 @@ void geo_ctx_destroy(geo_ctx* c) {
     if (c->sky) (void)hipFree(c->sky);
     if (c->disk_tex) (void)hipFree(c->disk_tex);
     if (c->emit_ramp) (void)hipFree(c->emit_ramp);
+    for (int i = 0; i < geo_ctx::kRenderStreams; ++i)
+        if (c->band_table[i]) (void)hipFree(c->band_table[i]);
     for (int b = 0; b < 2; ++b) {
         if (c->fan[b]) (void)hipFree(c->fan[b]);
         (void)hipEventDestroy(c->fan_written[b]);
@@ -727,6 +729,11 @@ struct RenderCall {
     // with GEO_FLAG_SS4 or without, any nframes, through the batched emission
     // kernels); the other entry points draw an emission frame alone
     bool emit_batch = false;
+    // geo_render_disk_ring_batch (GEO_FLAG_DISK scenes with geo_set_disk_ring_f64
+    // on, unshaded, shifted or with the emission, with GEO_FLAG_SS4 or without,
+    // any nframes, through the batched ring kernels); every other entry point
+    // refuses a batched or supersampled disk frame while the state is on
+    bool ring_batch = false;
     uint32_t width, height, row0, nrows, band_rows, band_stride;
     uint8_t* out_rgba8;
     uint8_t* out_mask = nullptr;  // (a batch draws colour only)
@@ -772,7 +779,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // and DEFER_STEPS at most, and a sample frame of twice the size that the
     // entry points take
     w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
-    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && !rc.emit_batch && rc.nframes != 1) ||
+    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && !rc.emit_batch && !rc.ring_batch && rc.nframes != 1) ||
                  scene->mode != GEO_MODE_DIRECT ||
                  (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
                  rc.out_uv || rc.out_steps || w.out_hits || w.out_g || w.out_q || rc.width > (1u << 19) ||
@@ -793,15 +800,20 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // or none: fill_frames' rule that a batch's flags agree); without the
     // emission set it has nothing to draw (GEO_ESTATE, after the disk's below)
     if (rc.emit_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
+    // geo_render_disk_ring_batch likewise; with the state off it has nothing
+    // to draw (GEO_ESTATE, after the disk's below)
+    if (rc.ring_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
     // geo_set_disk_emission: the one-frame entry points and geo_render_emission_batch
     // (through the older batched calls a disk frame would come out without
     // its emission: refused, nothing launched)
     w.emit = w.disk && c->emit_set;
     if (w.emit && (rc.disk_batch || rc.ss_batch)) return GEO_EINVAL;
     // geo_set_disk_ring_f64: the one-frame entry points' per-pixel renders
-    // only (a supersampled or batched disk frame would come out without its
-    // band: refused, nothing launched)
-    if (w.disk && c->disk_ring && (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch)) return GEO_EINVAL;
+    // and geo_render_disk_ring_batch only (through any other call a
+    // supersampled or batched disk frame would come out without its band:
+    // refused, nothing launched)
+    if (w.disk && c->disk_ring && !rc.ring_batch && (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch))
+        return GEO_EINVAL;
     // (no capture orbit, rs = 0: the state is ignored, the plain disk frame)
     w.disk_ring = w.disk && c->disk_ring && scene->rs > 0.0f && scene->r_obs > scene->rs;
     w.ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
@@ -829,6 +841,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if (w.disk) {
         if (!c->disk_set) return GEO_ESTATE;
         if (rc.emit_batch && !c->emit_set) return GEO_ESTATE;
+        if (rc.ring_batch && !c->disk_ring) return GEO_ESTATE;
         if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < c->disk.r_in)) ||
             !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
             return GEO_EINVAL;
@@ -864,6 +877,10 @@ static int fill_frames(const RenderCall& rc, RenderWork& w) {
         // GEO_FLAG_DISK's rules for this frame's observer (frame 0's in check_scene)
         if (w.disk && i > 0 && (!(si.rs == 0.0f || si.r_obs > si.rs) || !(si.r_obs < si.sphere_r)))
             return GEO_EINVAL;
+        // geo_set_disk_ring_f64 in a batch (geo_render_disk_ring_batch): the
+        // frames share rs and each has passed the rule above, so frame 0's
+        // w.disk_ring (rs > 0 and r_obs > rs: a capture orbit to draw) holds
+        // for every frame; each gets band constants of its own (launch_ring_frames)
         w.pk[i] = geo::make_consts(si.rs, si.sphere_r, si.r_obs, si.step, si.max_steps, si.tol);
         if (geo::geodesic_kind(w.pk[i]) != geo::geodesic_kind(w.pk[0])) return GEO_EINVAL;
     }
@@ -964,7 +981,8 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // (a GEO_FLAG_RING_F64 render learns its own order: its band's tiles cost
     // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's; an
     // emission render has a key of its own, as the disk render has, and a
-    // disk render with geo_set_disk_ring_f64 on, for its band's tiles)
+    // disk render with geo_set_disk_ring_f64 on, for its band's tiles, one
+    // frame or geo_render_disk_ring_batch's, whose frame 0 records them)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
                              (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u) |
                                  (w.emit ? 16u : 0u) | (w.disk_ring ? 32u : 0u),
@@ -1244,8 +1262,68 @@ static int launch_emit_frames(const geo_ctx* c, const RenderCall& rc, const Rend
     });
 }
 
+// Stage 5, geo_render_disk_ring_batch with a capture orbit to draw: the disk
+// batch's, the SS batch's disk frames' and the emission batch's launch with the
+// ring kernels.  Each frame's band constants come from the one-frame launch's
+// geo::band_consts (launch_disk_frame), at the sample frame's size under
+// GEO_FLAG_SS4, and reach the kernel through the device table of the call's
+// render-stream slot (geo_ctx::band_table), written on the call's stream by
+// geo_band_table_kernel just before the render launch: no host copy, no wait.
+static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(RingBatchArgs<kDiskEmit>) + sizeof(SsBatchOut) <=
+                  4096,
+              "kernel arguments fit 4 KiB");
+static int launch_ring_frames(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    DiskBatchArgs db;
+    DiskEmitBatchArgs eb;
+    if (const int st = fill_disk_batch(c, rc, w, db, w.emit ? &eb : nullptr)) return st;
+    BandTable bt;
+    std::memset(&bt, 0, sizeof(bt));
+    const uint32_t ssf = w.ss ? 2u : 1u;
+    for (uint32_t i = 0; i < rc.nframes; ++i)
+        bt.k[i] = geo::band_consts(rc.frames[i], rc.scene_per_frame ? rc.scene[i] : *rc.scene, ssf * rc.width,
+                                   ssf * rc.height);
+    void*& table = c->band_table[w.slot];
+    if (!table && hipMalloc(&table, sizeof(BandTable)) != hipSuccess) {
+        table = nullptr;
+        return GEO_ENOMEM;
+    }
+    geo::BandConsts* const bands = static_cast<geo::BandConsts*>(table);
+    hipLaunchKernelGGL(geo_band_table_kernel, dim3(rc.nframes), dim3(64), 0, w.p.s, bt, bands);
+    if (hipGetLastError() != hipSuccess) return GEO_EHIP;
+    SsBatchOut o;
+    o.out_width = rc.width;
+    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        if constexpr (KIND == geo::kFlat) {
+            return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
+        } else {
+            const auto run = [&](auto var, const auto& x) {
+                constexpr int VAR = decltype(var)::value;
+                if (w.ss)
+                    return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_ring_batch_kernel<KIND, VAR>, db, x,
+                                              o);
+                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_ring_batch_kernel<KIND, VAR>, db, x);
+            };
+            if (w.emit) {
+                RingBatchArgs<kDiskEmit> x;
+                x.bands = bands;
+                x.eb = eb;
+                return run(std::integral_constant<int, kDiskEmit>{}, x);
+            }
+            if (c->shift_set) return run(std::integral_constant<int, kDiskShift>{}, RingBatchArgs<kDiskShift>{bands});
+            return run(std::integral_constant<int, kDiskPlain>{}, RingBatchArgs<kDiskPlain>{bands});
+        }
+    });
+}
+
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    if (rc.ring_batch) {
+        // (no capture orbit, rs = 0: the state is ignored, the older batches' kernels)
+        if (w.disk_ring) return launch_ring_frames(c, rc, w);
+        if (w.emit) return launch_emit_frames(c, rc, w);
+        return w.ss ? launch_ss_frames(c, rc, w) : launch_disk_frames(c, rc, w);
+    }
     if (rc.emit_batch) return launch_emit_frames(c, rc, w);
     if (w.ss) return rc.ss_batch ? launch_ss_frames(c, rc, w) : launch_ss_frame(c, rc, w);
     if (w.disk) return rc.disk_batch ? launch_disk_frames(c, rc, w) : launch_disk_frame(c, rc, w);
@@ -1689,6 +1767,23 @@ int geo_render_emission_batch(geo_ctx* c, const geo_frame* frames, const geo_sce
     rc.scene_per_frame = true;
     rc.allow_disk = true;
     rc.emit_batch = true;
+    return render_impl(c, rc);
+}
+
+int geo_render_disk_ring_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                               unsigned long long* steps_total, void* stream) {
+    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
+        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
+        return invalid_call(c);
+    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
+                                out_rgba8, steps_total, stream);
+    rc.nframes = nframes;
+    rc.out_frame_stride = out_frame_stride;
+    rc.scene_per_frame = true;
+    rc.allow_disk = true;
+    rc.ring_batch = true;
     return render_impl(c, rc);
 }
 

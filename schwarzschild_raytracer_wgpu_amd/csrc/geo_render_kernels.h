@@ -1301,6 +1301,204 @@ __global__ __launch_bounds__(64) void geo_render_ss_emit_batch_kernel(const Rend
                                                          x.out_width);
 }
 
+// ---- the one body of the batched disk kernels with the f64 band -----------
+// geo_render_disk_ring_kernel's lanes (f32 lanes through
+// geo::geodesic_angle_disk and geo::disk_hits_f32, band lanes through
+// geo::disk_hits_band in a cold arm behind one ballot, then one
+// geo::disk_shade_hits) with wave_block_body's frame source, colour-only
+// output and SS4 resolve.  It varies along
+//   VAR    the shading: kDiskPlain, kDiskShift, kDiskEmit
+//   SS     GEO_FLAG_SS4, as in wave_block_body (the band's constants are then
+//          the sample frame's, and px, py the sample's)
+//   SRC    the frame source (DiskBatchFrame)
+// band_words: the frame's geo::BandConsts as 8-byte words in the context's
+// device table (geo_band_table_kernel); every workgroup copies them to LDS, one
+// word per thread, behind the wave-uniform padding return and one barrier.
+// The one-frame kernel above keeps the body it has: routed through this one
+// (with DiskFrame as its source and its side outputs as a property) its shaded
+// instantiations came out with 81 VGPRs instead of 80, five waves per SIMD
+// instead of six.
+template <int KIND, int VAR, bool SS, typename SRC>
+__device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& src, const uint2* band_words,
+                                               uint32_t out_width) {
+    static_assert(KIND != geo::kFlat, "no capture orbit without a black hole");
+    const uint32_t L = blockIdx.x;
+    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
+    const uint32_t wave = (L >> 3) & 3u;
+    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
+    const uint32_t tiles_x = a.tiles_x;
+    uint2 tile;
+    if (a.tile_order) {
+        const uint32_t t = a.tile_order[pos];
+        tile = make_uint2(t & 0xFFFFu, t >> 16);
+    } else {
+        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    // the band's constants in LDS: one 8-byte word per thread (kBandDwords / 2 <= 64)
+    __shared__ double band_lds[kBandDwords / 2u];
+    if (threadIdx.x < kBandDwords / 2u) reinterpret_cast<uint2*>(band_lds)[threadIdx.x] = band_words[threadIdx.x];
+    __syncthreads();
+    const geo::BandConsts& bkl = *reinterpret_cast<const geo::BandConsts*>(band_lds);
+    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
+    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
+    const uint32_t ly = wl0 + lane / kWaveW;
+    const uint32_t band = __umulhi(SS ? wl0 >> 1 : wl0, a.band_magic);  // (SS: on output rows, wave_block_body)
+    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
+    const bool in_frame = px < a.width && ly < a.nrows && py < a.height;
+    uint32_t steps = 0;
+    uint32_t colour = 0;  // SS: the sample's colour, kept in a register (a sample out of the frame does not return)
+    bool f64_lane = false;
+    if (in_frame) {
+        float c2x, c2y, c2z, g_obs = 1.0f;
+        if constexpr (VAR == kDiskPlain)
+            geo::pixel_central_dir(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y, &c2z);
+        else
+            geo::pixel_central_dir_g(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y,
+                                     &c2z, &g_obs);
+        const float st = geo::central_sin(c2z);
+        const float ct = geo::central_rho(c2x, c2y);
+        const float rct = geo::rcpf_(ct);
+        const geo::PixelConsts& k = src.consts();
+        const auto& dk = src.disk();
+        geo::DiskRay dr;
+        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+        f64_lane = geo::in_band(bkl.kx, ct);
+        float lam = 0.0f;
+        bool bh = false;
+        geo::DiskHits h;
+#pragma unroll
+        for (int c = 0; c < geo::kDiskMaxCrossings; ++c) {
+            h.hit[c] = false;
+            h.r[c] = 0.0f;
+        }
+        if (!f64_lane) {
+            float Uk[geo::kDiskMaxCrossings];
+            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            lam = geo::kPi2 - ang;
+            bh = lam < geo::kBlackHoleLambda;
+            geo::disk_hits_f32(dk, k, dr, Uk, steps, ang, &h);
+        }
+        if (geo::ballot_(f64_lane) != 0) {
+            if (f64_lane) {
+                GEO_COLD_ARM();
+                const double l = geo::disk_hits_band(bkl, dk, dr, px, py, &steps, &h);
+                lam = (float)l;
+                bh = l < (double)geo::kBlackHoleLambda;
+            }
+        }
+        float U = 0.0f, V = 0.0f;
+        if (!bh) geo::sky_uv(src.central_to_uv(), c2x, c2y, ct, rct, lam, &U, &V);
+        const uint32_t base =
+            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
+        const auto& t = src.tex();
+        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(t.tex), 0, (int)t.tex_bytes,
+                                                                    kBufferRsrcWord3),
+                                  t.tex_pitch_b};
+        const auto dsample = [&](float Ud, float Vd) {
+            return geo::sample_sky_quad_f(dquad, t.tex_w256, t.tex_h256, Ud, Vd);
+        };
+        float* const none = nullptr;  // a batch draws colour only: no hits, g or q
+        if constexpr (VAR == kDiskEmit) {
+            const auto rfetch = [ramp = src.ramp()](uint32_t i) { return ramp[i]; };
+            const auto& ek = src.emission();
+            geo::DiskShiftRay sr;
+            geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
+            colour = geo::disk_shade_hits(dk, dr, h, base, geo::disk_colour_emit(dk, k, ek, sr, dsample, rfetch), none,
+                                          none, none);
+        } else if constexpr (VAR == kDiskShift) {
+            const auto& sk = src.shift();
+            geo::DiskShiftRay sr;
+            geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
+            colour = geo::disk_shade_hits(dk, dr, h, base, geo::disk_colour_shift(k, sk, sr, dsample), none, none, none);
+        } else {
+            colour = geo::disk_shade_hits(dk, dr, h, base, geo::disk_colour_plain(dsample), none, none, none);
+        }
+        if constexpr (!SS) a.out_rgba[src.out_base() + (size_t)ly * a.width + px] = colour;
+    }
+    // every per-lane arm has rejoined: all 64 lanes are active, as the
+    // resolve's exchange and the wave reductions need
+    if constexpr (SS) {
+        const uint32_t resolved = ss_resolve(colour);
+        if (in_frame && (lane & 0x11u) == 0u)
+            a.out_rgba[src.out_base() + (size_t)(ly >> 1) * out_width + (px >> 1)] = resolved;
+    }
+    // wave_block_body's epilogue with the ring kernel's tile cost: the wave runs its
+    // f32 lanes' loop, then its band lanes' f64 loop at about twice the cost
+    // per step
+    if (a.step_slots) {
+        const uint32_t total = wave_sum_u32(steps);
+        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
+        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
+    }
+    if (a.tile_cost && src.records_cost()) {
+        const uint32_t wmax = wave_max_u32(f64_lane ? 0u : steps) + 2u * wave_max_u32(f64_lane ? steps : 0u);
+        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
+    }
+}
+
+// ---- geo_render_disk_ring_batch: up to kMaxBatchFrames ring frames in one launch --
+// The disk batch, the SS batch's disk frames and the emission batch (VAR) with
+// the band's lanes in f64: disk_ring_body on DiskBatchFrame, the frame in
+// blockIdx.z.  The argument segment has no room for eight frames'
+// geo::BandConsts (8 x 344 bytes beside DiskBatchArgs' 3312), nor for the
+// display_to_movement rows they are derived from, so the host computes them
+// with the one-frame launch's geo::band_consts (at twice the size under SS4) and
+// geo_band_table_kernel, which takes them by value, writes them to the
+// context's device table of the call's render-stream slot just before the
+// render launch on the same stream; workgroups of frame z copy table[z] to LDS.
+struct BandTable {
+    geo::BandConsts k[kMaxBatchFrames];
+};
+static_assert(sizeof(BandTable) == kMaxBatchFrames * 344u && sizeof(BandTable) <= 4096 - 16, "the table by value");
+__global__ __launch_bounds__(64) void geo_band_table_kernel(const BandTable t, geo::BandConsts* out) {
+    // one workgroup per frame, one 8-byte word per thread
+    if (threadIdx.x < kBandDwords / 2u)
+        reinterpret_cast<uint2*>(out + blockIdx.x)[threadIdx.x] =
+            reinterpret_cast<const uint2*>(&t.k[blockIdx.x])[threadIdx.x];
+}
+
+template <int VAR>
+struct RingBatchArgs {
+    const geo::BandConsts* bands;  // the table: frame z's constants at bands[z]
+};
+template <>
+struct RingBatchArgs<kDiskEmit> {
+    const geo::BandConsts* bands;
+    DiskEmitBatchArgs eb;
+};
+
+template <int KIND, int VAR, bool SS>
+__device__ __forceinline__ void disk_ring_batch(const RenderArgs& a, const DiskBatchArgs& db,
+                                                const RingBatchArgs<VAR>& x, uint32_t out_width) {
+    const uint2* const words = reinterpret_cast<const uint2*>(x.bands + blockIdx.z);
+    if constexpr (VAR == kDiskEmit)
+        disk_ring_body<KIND, VAR, SS>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, x.eb, blockIdx.z}, words,
+                                             out_width);
+    else
+        disk_ring_body<KIND, VAR, SS>(a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, words, out_width);
+}
+
+// (amdgpu_waves_per_eu: the one-frame ring kernels' six waves per SIMD as the
+// allocator's target.  Left to itself it gave the emission instantiations 81
+// VGPRs, one over the class, for the lanes of an SGPR it moved to a VGPR: a
+// batch reads its frame's constants through db.f[z] and holds more scalars
+// (106) than the one-frame kernel (100).  With the target they take 80, the
+// others are unchanged, and none uses scratch; profiles/disk_ring_batch_isa.txt.)
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void geo_render_disk_ring_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                        const RingBatchArgs<VAR> x) {
+    disk_ring_batch<KIND, VAR, false>(a, db, x, 0u);
+}
+
+// The same with GEO_FLAG_SS4: a lane per sample of the 2W x 2H ring render.
+template <int KIND, int VAR>
+__global__ __launch_bounds__(64) void geo_render_ss_ring_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                      const RingBatchArgs<VAR> x,
+                                                                      const SsBatchOut o) {
+    disk_ring_batch<KIND, VAR, true>(a, db, x, o.out_width);
+}
+
 
 // ---- longest-first dispatch: the order from recorded tile costs ---------
 // Cost classes of an eighth of an octave (the octave and the next three
@@ -1748,6 +1946,18 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, kDiskShift>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedOut, kDiskEmit>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, kDiskEmit>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskPlain>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskPlain>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskShift>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskShift>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskEmit>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskEmit>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskPlain>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskPlain>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskShift>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskShift>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskEmit>;
+    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskEmit>;
 }
 
 }  // namespace

@@ -217,7 +217,7 @@ class ShardedFrame:
     def __init__(self, ctx, frame, scene, width: int, height: int, band_rows: int, rank: int, world: int, device,
                  dist=None, host_gather: bool = False, frames_per_gather: int = 1, render_streams: int = 1,
                  present_rgb: bool = True, lead: int = 1, batch_launch: bool = False, peer_bands: int = 1,
-                 emission_batch: bool = False):
+                 emission_batch: bool = False, disk_ring_batch: bool = False):
         """host_gather: stage through host memory (gloo backend; rehearsals only).
         present_rgb: peers send RGB24 (geo_pack_rgb after each render; 25 %
         fewer bytes on the links) when the width is a multiple of 4.
@@ -233,7 +233,12 @@ class ShardedFrame:
         emission_batch: with batch_launch, a GEO_FLAG_DISK scene of a context
         with set_disk_emission on goes to geo_render_emission_batch (with
         GEO_FLAG_SS4 or without); without it such a scene is refused, as the
-        older batched entry points refuse it."""
+        older batched entry points refuse it.
+        disk_ring_batch: with batch_launch, a GEO_FLAG_DISK scene of a context
+        with set_disk_ring_f64 on goes to geo_render_disk_ring_batch (with
+        GEO_FLAG_SS4 or without, with the emission set or not: emission_batch
+        is then not needed); without it such a scene is refused, as every
+        other batched entry point refuses it."""
         import torch
 
         from ._lib import lib
@@ -253,11 +258,12 @@ class ShardedFrame:
 
         self.batch = bool(batch_launch) and self.K > 1
         self.emission_batch = bool(emission_batch)
+        self.disk_ring_batch = bool(disk_ring_batch)
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
         if self.batch:
-            self._refuse_emission_batch(scene)
             self._refuse_ring_batch(scene)
+            self._refuse_emission_batch(scene)
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
         self.pending_scenes = []     # and copies of their scenes (they differ in r_obs at most)
         self._pending_key = b""
@@ -349,26 +355,34 @@ class ShardedFrame:
         return bool(scene is not None and scene.flags & GEO_FLAG_DISK
                     and getattr(self.ctx, "disk_emission_set", False))
 
+    def _ring_scene(self, scene) -> bool:
+        """A GEO_FLAG_DISK scene of a context with set_disk_ring_f64 on."""
+        from ._lib import GEO_FLAG_DISK
+
+        return bool(scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_ring_f64", False))
+
     def _refuse_emission_batch(self, scene) -> None:
         """The older batched entry points draw no emission frames
         (geo_set_disk_emission, geo.h): without emission_batch a GEO_FLAG_DISK
         scene of a context with the emission set is refused here, by name,
-        instead of by the launch's GEO_EINVAL."""
+        instead of by the launch's GEO_EINVAL.  (With disk_ring_batch a ring
+        scene goes to geo_render_disk_ring_batch, which draws the emission.)"""
+        if self.disk_ring_batch and self._ring_scene(scene):
+            return
         if not self.emission_batch and self._emission_scene(scene):
             raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on through the older batched "
                              "entry points: pass emission_batch=True (geo_render_emission_batch), or use "
                              "batch_launch=False, or clear_disk_emission()")
 
     def _refuse_ring_batch(self, scene) -> None:
-        """No batched entry point draws a disk frame's f64 band
-        (geo_set_disk_ring_f64, geo.h): a GEO_FLAG_DISK scene of a context
-        with set_disk_ring_f64 on is refused here, by name, instead of by the
-        launch's GEO_EINVAL."""
-        from ._lib import GEO_FLAG_DISK
-
-        if scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_ring_f64", False):
-            raise ValueError("batch_launch=True cannot draw a disk with set_disk_ring_f64 on: the batched entry "
-                             "points refuse it; use batch_launch=False, or set_disk_ring_f64(False)")
+        """Only geo_render_disk_ring_batch draws a batched disk frame's f64
+        band (geo_set_disk_ring_f64, geo.h): without disk_ring_batch a
+        GEO_FLAG_DISK scene of a context with set_disk_ring_f64 on is refused
+        here, by name, instead of by the launch's GEO_EINVAL."""
+        if not self.disk_ring_batch and self._ring_scene(scene):
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_ring_f64 on through the older "
+                             "batched entry points: pass disk_ring_batch=True (geo_render_disk_ring_batch), or use "
+                             "batch_launch=False, or set_disk_ring_f64(False)")
 
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
@@ -376,7 +390,9 @@ class ShardedFrame:
         in one launch (geo_render_band_set_batch, geo_render_ss_batch for
         GEO_FLAG_SS4 scenes, or geo_render_disk_batch for GEO_FLAG_DISK
         scenes without it; with emission_batch, geo_render_emission_batch for
-        a disk scene while the emission is set), on `stream` (a handle;
+        a disk scene while the emission is set; with disk_ring_batch,
+        geo_render_disk_ring_batch for a disk scene while set_disk_ring_f64
+        is on), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
         from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4, GeoFrame, GeoScene, check
@@ -398,9 +414,11 @@ class ShardedFrame:
         # supersampled scenes (with a disk or without) and thin-disk scenes
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
-        self._refuse_emission_batch(scenes[0])
         self._refuse_ring_batch(scenes[0])
-        if self.emission_batch and self._emission_scene(scenes[0]):
+        self._refuse_emission_batch(scenes[0])
+        if self.disk_ring_batch and self._ring_scene(scenes[0]):
+            name = "geo_render_disk_ring_batch"  # (with GEO_FLAG_SS4 or without, any shading)
+        elif self.emission_batch and self._emission_scene(scenes[0]):
             name = "geo_render_emission_batch"  # (with GEO_FLAG_SS4 or without)
         elif scenes[0].flags & GEO_FLAG_SS4:
             name = "geo_render_ss_batch"

@@ -71,6 +71,20 @@ spread ((max - min) / median of its alternation medians) and whether each
 cost lies beyond twice that spread.  One JSON object.
 
   python tools/bench_disk.py --ring [--out profiles/disk_ring_bench_cfg3.json]
+
+--batch K --ring measures the batched launch of disk frames with the f64 band
+(geo_render_disk_ring_batch, geo_set_disk_ring_f64 on, unshaded) on --batch's
+layout, by --batch K --emission's method: one launch of K ring frames (the
+small kernel that writes the frames' band constants runs on the stream before
+the render: the stream events see it, the dispatch's own event pair does not)
+alternates with K one-frame geo_render_band_set launches of the same frames
+back to back with the state on (the yardstick), each on its own context;
+--alternations (5) times --n (30) samples of each side per timing after
+--settle (4) alternations kept apart, --sessions (2) sessions.  The batch
+counts as a gain where it is faster than the one-frame side by more than twice
+that side's alternation spread.
+
+  python tools/bench_disk.py --batch 8 --ring [--out profiles/disk_ring_batch_bench_cfg3.json]
 """
 from __future__ import annotations
 
@@ -106,7 +120,8 @@ def main():
     p.add_argument("--out")
     args = p.parse_args()
     if not args.out:
-        name = "disk_ring_bench_cfg3.json" if args.ring else "disk_emission_batch_bench_cfg3.json" if (
+        name = "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
+            args.ring) else "disk_emission_batch_bench_cfg3.json" if (
             args.batch and args.emission) else (
             "disk_batch_bench_cfg3.json") if args.batch else (
             "disk_emission_bench_cfg3.json" if args.emission else (
@@ -114,6 +129,8 @@ def main():
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.batch and args.ring:
+        return ring_batch_main(args)
     if args.ring:
         return ring_main(args)
     if args.batch and args.emission:
@@ -670,6 +687,136 @@ def emission_batch_main(args):
                   "(max - min) / median of a side's alternation medians; margin = 1 - 2 x the one-frame side's spread",
         "sessions": [emission_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission)
                      for _ in range(args.sessions)],
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+def ring_batch_session(args, cfg, frame, scene, sky, tex):
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.dist import BandLayout
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent, hipEventDefault
+
+    K = args.batch
+    W, H = cfg.width, cfg.height
+    L = BandLayout(H, 8, 8, 1)  # a peer's share at N = 8
+    band = (L.band_height(), L.row0(), L.cycle_rows, L.nbands())
+    packed = L.packed_rows() * W * 4
+    dev = torch.device("cuda:0")
+    out = torch.empty(K * packed, dtype=torch.uint8, device=dev)
+    sh = torch.cuda.current_stream().cuda_stream
+    frames = (_lib.GeoFrame * K)(*([frame] * K))
+    scenes = (_lib.GeoScene * K)(*([scene] * K))
+    lib = _lib.lib
+
+    def make_ctx():
+        c = g.Context(0)
+        c.set_sky(sky)
+        c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+        c.set_disk_ring_f64(True)
+        return c
+
+    def run_batch(c, pairs=None):
+        if pairs is not None:
+            c.time_next_render(*pairs[0])
+        _lib.check("geo_render_disk_ring_batch", lib.geo_render_disk_ring_batch(
+            c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
+
+    def run_singles(c, pairs=None):
+        for k in range(K):
+            if pairs is not None:
+                c.time_next_render(*pairs[k])
+            _lib.check("geo_render_band_set", lib.geo_render_band_set(
+                c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None,
+                None, None, sh))
+
+    # (each side on its own context: the learned dispatch order is kept per context)
+    sides = [("ring_batch", make_ctx(), run_batch, 1), ("ring_single", make_ctx(), run_singles, K)]
+    for _ in range(args.warmup):
+        for _, c, run, _ in sides:
+            run(c)
+    torch.cuda.synchronize()
+    res = {"layout": {"world": 8, "rank": 1, "band_rows": band[0], "row0": band[1], "row_stride": band[2],
+                      "nbands": band[3], "rows": L.rows_mine()}}
+    for how in ("stream_events", "dispatch_events"):
+        med = {name: [] for name, *_ in sides}
+        settling = {name: [] for name, *_ in sides}
+        for alt in range(args.settle + args.alternations):
+            ev = {name: [] for name, *_ in sides}
+            for _ in range(args.n):
+                for name, c, run, m in sides:
+                    if how == "stream_events":
+                        a, b = HipEvent(hipEventDefault), HipEvent(hipEventDefault)
+                        a.record(sh)
+                        run(c)
+                        b.record(sh)
+                        ev[name].append([(a, b)])
+                    else:
+                        pairs = [(HipEvent(), HipEvent()) for _ in range(m)]
+                        run(c, pairs)
+                        ev[name].append(pairs)
+                torch.cuda.synchronize()  # the next sample's launches queue behind nothing
+            for name, v in ev.items():
+                (settling if alt < args.settle else med)[name].append(
+                    float(np.median([sum(a.elapsed_time(b) for a, b in pairs) for pairs in v]) / K))
+        b_m, s_m = float(np.median(med["ring_batch"])), float(np.median(med["ring_single"]))
+        spread = (max(med["ring_single"]) - min(med["ring_single"])) / s_m
+        res[how] = {
+            "settling_alternations_not_counted": settling,
+            "ring_batch_ms_per_frame_medians": med["ring_batch"],
+            "ring_single_ms_per_frame_medians": med["ring_single"],
+            "ring_batch_ms_per_frame": b_m, "ring_single_ms_per_frame": s_m,
+            "batch_over_single": b_m / s_m, "single_spread": spread,
+            "batch_spread": (max(med["ring_batch"]) - min(med["ring_batch"])) / b_m,
+            # the batch is held to a saving of more than twice the one-frame side's own spread
+            "margin": 1.0 - 2.0 * spread, "faster_by_more_than_margin": bool(b_m < s_m * (1.0 - 2.0 * spread)),
+        }
+    for _, c, *_ in sides:
+        c.close()
+    return res
+
+
+def ring_batch_main(args):
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
+
+    K = args.batch
+    if not 1 <= K <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise SystemExit(f"--batch: 1 .. {_lib.GEO_MAX_BATCH_FRAMES}")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg = CONFIGS["cfg3_4k"]
+    obs = g.Observer(cfg.rs, cfg.fov, cfg.width, cfg.height)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg.step, cfg.max_steps,
+                         flags=_lib.GEO_FLAG_DISK)
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    res = {
+        "config": "cfg3_4k", "width": cfg.width, "height": cfg.height, "max_steps": cfg.max_steps,
+        "disk": [1.6 * cfg.rs, 2.2 * cfg.rs], "disk_ring_f64": True,
+        "frames_per_batch": K, "n": args.n, "alternations": args.alternations, "settle": args.settle,
+        "order_in_a_sample": ["ring_batch", "ring_single"], "warmup": args.warmup,
+        "timing": "stream_events: a pair of events on the stream around one geo_render_disk_ring_batch call of K frames "
+                  "(the band-table kernel and the render launch), or around K one-frame geo_render_band_set launches "
+                  "back to back; dispatch_events: geo_time_next_render pairs on the render dispatches alone, the K "
+                  "one-frame times added; the two sides alternate, each on its own context; per alternation the median "
+                  "of n, after settle alternations of each timing that are kept apart; spread = (max - min) / median of "
+                  "a side's alternation medians; margin = 1 - 2 x the one-frame side's spread",
+        "sessions": [ring_batch_session(args, cfg, frame, scene, sky, tex) for _ in range(args.sessions)],
     }
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
