@@ -227,6 +227,8 @@ def composite_np(s, d):
 
 
 def test_compositing(cpu, curved):
+    """(One colour for every slot cannot see the order of the images:
+    tests/test_sampler_cpu.py::test_disk and its `disk_order_reversed` mutation do.)"""
     a, p, _, _, _ = curved["A"]
     nohit = ~(a["hits"][..., 0] > 0.0).any(axis=-1)
     assert nohit.any() and (~nohit).any()
