@@ -65,7 +65,9 @@ extern "C" {
                                    geo_render_emission_batch;
                                    announced by GEO_HAS_DISK_RING_F64: geo_set_disk_ring_f64;
                                    announced by GEO_HAS_DISK_RING_BATCH:
-                                   geo_render_disk_ring_batch) */
+                                   geo_render_disk_ring_batch;
+                                   announced by GEO_HAS_DISK_ADAPTIVE:
+                                   geo_render_disk_adaptive) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -75,6 +77,7 @@ extern "C" {
 #define GEO_HAS_DISK_EMISSION_BATCH 1
 #define GEO_HAS_DISK_RING_F64 1
 #define GEO_HAS_DISK_RING_BATCH 1
+#define GEO_HAS_DISK_ADAPTIVE 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -150,7 +153,9 @@ typedef enum geo_status {
                                    geo_render_disk_batch for up to GEO_MAX_BATCH_FRAMES in
                                    one launch (the multi-GPU pipeline's batches, a moving
                                    observer's frames); geo_render_band_set_frames / _batch
-                                   refuse the flag.  GEO_MODE_DIRECT,
+                                   refuse the flag.  GEO_MODE_DIRECT (GEO_MODE_ADAPTIVE
+                                   through geo_render_disk_adaptive alone, whose comment
+                                   states the crossing rule of that mode),
                                    with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
                                    and rs < r_in; r_out < sphere_r and r_obs < sphere_r
                                    (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
@@ -161,7 +166,7 @@ typedef enum geo_status {
                                    through f64 by the context state geo_set_disk_ring_f64
                                    (mask, UV, steps and steps_total are then the plain
                                    GEO_FLAG_RING_F64 render's).  Follow-ups, not in this ABI:
-                                   GEO_MODE_ADAPTIVE, GEO_FLAG_MIPS / _COMPOSITE.
+                                   GEO_FLAG_MIPS / _COMPOSITE.
                                    With geo_set_disk_shift the hits are shaded by their
                                    Doppler and redshift factor. */
 #define GEO_FLAG_SS4 32u        /* (a build extension, not in the reference) 2 x 2 supersampling,
@@ -660,6 +665,46 @@ int geo_render_disk_ring_batch(geo_ctx* ctx, const geo_frame* frames, const geo_
                                uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                                uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                                unsigned long long* steps_total, void* stream);
+
+/* The thin disk in GEO_MODE_ADAPTIVE (GEO_HAS_DISK_ADAPTIVE): one GEO_FLAG_DISK
+ * frame of the context's disk drawn by the error-controlled integrator,
+ * unshaded, with geo_set_disk_shift or with geo_set_disk_emission (which takes
+ * the shift's place, as everywhere else).  The layout and the output rules are
+ * geo_render_band_set's; a row range is the one-band case: with nbands == 1,
+ * band_rows is any number of rows from 1 to 2^20 (clipped to height; row_stride
+ * is not read).  All per-pixel outputs work, and the buffers armed by
+ * geo_disk_hits_next_render, geo_disk_shift_next_render and
+ * geo_disk_emission_next_render are written as in the one-frame direct render.
+ * mask, UV, steps and steps_total (or the deferred accumulator) are those of
+ * the plain GEO_MODE_ADAPTIVE render of the same scene without GEO_FLAG_DISK,
+ * bit for bit: the integration is that render's, attempt for attempt.
+ * The crossings are GEO_FLAG_DISK's, a_k = a_0 + k pi.  The integrator's
+ * accepted steps tile the traveled angle; crossing k is probed in the accepted
+ * attempt whose span [ang, ang + h) holds a_k, while the ray is still
+ * integrating (its stopping attempt counts; a rejected attempt probes nothing),
+ * by one RK5 step of length a_k - ang from the attempt's start state.  A probed
+ * crossing is a hit when a_k lies before the returned traveled angle and
+ * r_in <= r <= r_out there; everything after r is the direct mode's
+ * (csrc/geo_disk.h).
+ * The scene carries GEO_MODE_ADAPTIVE and GEO_FLAG_DISK, with
+ * GEO_FLAG_DEFER_STEPS at most, and tol under the adaptive mode's rules;
+ * GEO_EINVAL for a GEO_MODE_DIRECT or GEO_MODE_FAN scene (the older calls draw
+ * those) and wherever a GEO_FLAG_DISK rule is broken (rs == 0, or r_obs > rs
+ * and rs < r_in; r_out < sphere_r; r_obs < sphere_r; with a shift or an
+ * emission set and rs > 0, r_in > 1.5 rs).  GEO_ESTATE without a sky or a disk.
+ * GEO_EINVAL while geo_set_disk_ring_f64 is on and rs > 0: the frame would come
+ * out without its band (with rs == 0 the state is ignored).  A refused call
+ * launches nothing, writes nothing and consumes the armed buffers and the
+ * timing pair.  geo_time_next_render, geo_set_dispatch (the learned order has
+ * a grid key of its own; a tile's cost is in attempts) and geo_set_tile_order
+ * work as for the one-frame direct render.  Not in this ABI: batched adaptive
+ * disk frames and the multi-GPU pipeline, GEO_FLAG_SS4 and the f64 capture
+ * band with the adaptive disk.  Every older call keeps every refusal it has.
+ * Asynchronous on `stream`. */
+int geo_render_disk_adaptive(geo_ctx* ctx, const geo_frame* frame, const geo_scene* scene, uint32_t width,
+                             uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                             uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
+                             uint32_t* out_steps, unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

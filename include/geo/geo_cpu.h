@@ -118,6 +118,26 @@ int geo_render_cpu_disk_shift_ring_f64(const geo_frame* frame, const geo_scene* 
                                        uint32_t disk_h, float* out_hits, const geo_disk_shift* shift, float* out_g,
                                        int ring_f64);
 
+/* The disk frame in GEO_MODE_ADAPTIVE (geo.h, geo_render_disk_adaptive):
+ * geo_render_cpu_disk_emission's arguments and a trailing shift.  emission
+ * non-NULL draws the emission and takes the shift's place, as on the device
+ * (shift is then not read); otherwise shift non-NULL draws the shifted disk;
+ * both NULL, the unshaded one.  out_g is written with either, out_q with the
+ * emission.  The scene carries GEO_MODE_ADAPTIVE and GEO_FLAG_DISK, with
+ * GEO_FLAG_DEFER_STEPS at most, under the device's rules (GEO_EINVAL for a
+ * GEO_MODE_DIRECT or GEO_MODE_FAN scene, for GEO_FLAG_SS4 and for a broken
+ * disk, shift or emission rule); every other geo_render_cpu_disk* function
+ * keeps refusing the adaptive mode.  It runs the kernels' header
+ * (geo::geodesic_angle_adaptive_disk): output equal to the GPU's bit for bit. */
+int geo_render_cpu_disk_adaptive(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                 uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan, uint32_t width,
+                                 uint32_t height, uint32_t row0, uint32_t nrows, uint32_t row_step, int threads,
+                                 uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                                 unsigned long long* steps_total, const geo_disk* disk, const uint8_t* disk_rgba8,
+                                 uint32_t disk_w, uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                 const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q,
+                                 const geo_disk_shift* shift);
+
 #ifdef __cplusplus
 }
 #endif

@@ -453,6 +453,20 @@ class Context:
             _ptr(out_rgba), _ptr(out_mask), _ptr(out_uv), _ptr(out_steps), _ptr(steps_total),
             _stream_handle(stream)))
 
+    def render_disk_adaptive(self, frame: GeoFrame, scene: GeoScene, width: int, height: int, band_rows: int,
+                             row0: int, row_stride: int, nbands: int, out_rgba, out_mask=None, out_uv=None,
+                             out_steps=None, steps_total=None, stream=None) -> None:
+        """geo_render_disk_adaptive: the context's thin disk in GEO_MODE_ADAPTIVE (scene.flags carries
+        GEO_FLAG_DISK), render_band_set's layout and outputs; nbands == 1 draws the band_rows rows from
+        row0 on, any number of them.  The buffers armed by disk_hits_next_render, disk_shift_next_render
+        and disk_emission_next_render are written as in the one-frame direct render."""
+        nrows = nbands * band_rows
+        _check_outputs(nrows, width, out_rgba, out_mask, out_uv, out_steps, steps_total)
+        check("geo_render_disk_adaptive", lib.geo_render_disk_adaptive(
+            self._h, ctypes.byref(frame), ctypes.byref(scene), width, height, band_rows, row0, row_stride, nbands,
+            _ptr(out_rgba), _ptr(out_mask), _ptr(out_uv), _ptr(out_steps), _ptr(steps_total),
+            _stream_handle(stream)))
+
 
 def _check_outputs(nrows: int, width: int, rgba, mask, uv, steps, steps_total) -> None:
     """The kernel writes 4 B of RGBA8, 1 B of mask, 2 f32 of UV and one u32 of

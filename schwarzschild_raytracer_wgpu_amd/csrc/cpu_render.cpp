@@ -59,6 +59,9 @@ struct CpuJob {
     // geo_render_cpu_disk_ring_f64 (geo_set_disk_ring_f64): the disk's band
     // lanes take the f64 path (`band` above holds its constants)
     bool dring;
+    // geo_render_cpu_disk_adaptive: the disk frame in GEO_MODE_ADAPTIVE
+    // (geo::geodesic_angle_adaptive_disk)
+    bool dadaptive;
 };
 
 float geodesic(const CpuJob& j, float st, float ct, float rct, uint32_t* n) {
@@ -187,7 +190,10 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             const float ct = geo::central_rho(c2x, c2y);
             const float rct = geo::rcpf_(ct);
             geo::DiskRay dr;
-            geo::disk_ray(j.dk, k, c2x, c2y, ct, rct, &dr);
+            if (j.dadaptive)
+                geo::disk_ray_adaptive(j.dk, k, c2x, c2y, ct, rct, &dr);
+            else
+                geo::disk_ray(j.dk, k, c2x, c2y, ct, rct, &dr);
             uint32_t n = 0;
             if (j.dring) {
                 // geo_render_disk_ring_kernel per pixel: the band's lanes by
@@ -242,10 +248,27 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             }
             float Uk[geo::kDiskMaxCrossings];
             float ang;
-            switch (geo::geodesic_kind(k)) {
-                case geo::kCurvedOut: ang = geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk); break;
-                case geo::kCurvedIn: ang = geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk); break;
-                default: ang = geo::geodesic_angle_disk<geo::kFlat>(k, st, ct, rct, dr, &n, Uk);
+            if (j.dadaptive) {
+                // geo_render_disk_adaptive's kernels per pixel
+                switch (geo::geodesic_kind(k)) {
+                    case geo::kCurvedOut:
+                        ang = geo::geodesic_angle_adaptive_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk);
+                        break;
+                    case geo::kCurvedIn:
+                        ang = geo::geodesic_angle_adaptive_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
+                        break;
+                    default: ang = geo::geodesic_angle_adaptive_disk<geo::kFlat>(k, st, ct, rct, dr, &n, Uk);
+                }
+            } else {
+                switch (geo::geodesic_kind(k)) {
+                    case geo::kCurvedOut:
+                        ang = geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk);
+                        break;
+                    case geo::kCurvedIn:
+                        ang = geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
+                        break;
+                    default: ang = geo::geodesic_angle_disk<geo::kFlat>(k, st, ct, rct, dr, &n, Uk);
+                }
             }
             const float lam = geo::kPi2 - ang;
             const bool bh = lam < geo::kBlackHoleLambda;
@@ -376,7 +399,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
                     const uint8_t* disk_rgba8, uint32_t disk_w, uint32_t disk_h, float* out_hits,
                     const geo_disk_shift* shift, float* out_g, const geo_disk_emission* emission = nullptr,
                     const uint8_t* ramp_rgba8 = nullptr, uint32_t ramp_n = 0, float* out_q = nullptr,
-                    bool ring_f64 = false) {
+                    bool ring_f64 = false, bool disk_adaptive = false) {
     if (!frame || !scene || !sky_rgba8 || !out_rgba8 || sky_w == 0 || sky_h == 0 || width == 0 || height == 0 ||
         row_step == 0 || width > (1u << 20) || height > (1u << 20))
         return GEO_EINVAL;
@@ -405,8 +428,10 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
         return GEO_EINVAL;
     if (disk) {
         // geo_render_rows' GEO_FLAG_DISK rules and geo_set_disk's (geo.h)
-        if ((scene->flags & GEO_FLAG_DISK) == 0 || scene->mode != GEO_MODE_DIRECT ||
-            (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0)
+        // (geo_render_cpu_disk_adaptive: GEO_MODE_ADAPTIVE, and no GEO_FLAG_SS4)
+        if ((scene->flags & GEO_FLAG_DISK) == 0 ||
+            scene->mode != (disk_adaptive ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
+            (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | (disk_adaptive ? 0u : GEO_FLAG_SS4))) != 0)
             return GEO_EINVAL;
         if (!disk_rgba8 || disk_w == 0 || disk_h == 0 || disk_w > (1u << 20) || disk_h > (1u << 20) ||
             ((uint64_t)disk_w + 2u) * ((uint64_t)disk_h + 2u) * 4u >= (1ull << 31))
@@ -476,6 +501,7 @@ int render_cpu_impl(const geo_frame* frame, const geo_scene* scene, const uint8_
     j.dring = disk && ring_f64 && scene->rs > 0.0f && scene->r_obs > scene->rs;
     if (j.ring || j.dring) j.band = geo::band_consts(*frame, *scene, width, height);  // (never with GEO_FLAG_SS4)
     j.disk = disk != nullptr;
+    j.dadaptive = disk && disk_adaptive;
     j.dtex = nullptr;
     j.dw = disk_w;
     j.dh = disk_h;
@@ -627,4 +653,21 @@ extern "C" int geo_render_cpu_disk_shift_ring_f64(const geo_frame* frame, const 
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
                            disk_h, out_hits, shift, shift || ss ? out_g : nullptr, nullptr, nullptr, 0, nullptr,
                            ring_f64 != 0);
+}
+
+extern "C" int geo_render_cpu_disk_adaptive(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                            uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                            uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                            uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                            float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                            const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                            uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                            const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q,
+                                            const geo_disk_shift* shift) {
+    if (!disk) return GEO_EINVAL;
+    // (the emission takes the shift's place, as on the device)
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, emission ? nullptr : shift, emission || shift ? out_g : nullptr, emission,
+                           ramp_rgba8, n, emission ? out_q : nullptr, false, true);
 }

@@ -694,4 +694,141 @@ GEO_HD auto disk_colour_emit(const DiskConsts& d, const PixelConsts& k, const Di
     };
 }
 
+// ---- The disk in GEO_MODE_ADAPTIVE (geo_render_disk_adaptive) -------------
+// geodesic_angle_adaptive (geo_pixel.h) with the crossing probes.  The traveled
+// angle and *steps (attempts) are geodesic_angle_adaptive's, bit for bit, for
+// every ray: the set-up, the step control, the wave-uniform `live` loop with
+// its single exit edge, the stop test and the Newton finish are its own.  The
+// f32 specification of the probes:
+//   * the crossings a_k = fma(k, pi, a_0), k < 3, are disk_ray's; its nodes jn
+//     and partial steps dn belong to the fixed grid and are not read, except
+//     that "no crossing" is still jn[0] == 0xFFFFFFFF
+//   * the loop's accepted steps tile the angle axis with its own f32 values:
+//     an accepted attempt goes from ang to ang' = ang + h, the f32 sum the
+//     loop forms
+//   * crossing k is probed in the one accepted attempt with ang <= a_k < ang',
+//     and only while the lane is still in `live` at that attempt (the lane's
+//     stopping attempt counts): no probe in a rejected attempt, none after
+//     the lane has left `live`, none when geodesic_init ends the ray before
+//     the loop
+//   * the probe is U of dp5_step<KIND>(U, V, d, d d), d = a_k - ang (an f32
+//     subtract), from the attempt's start state: the form the Newton finish
+//     uses for an arbitrary step length
+//   * hmax = 16 step can exceed pi (step 0.3: 4.8), so one accepted step can
+//     hold two or three crossings: the arm loops while (a_next < ang')
+//   * an unprobed crossing has U = 0 (never in [u_lo, u_hi]: u_lo > 0)
+//   * a probed crossing is a hit when a_k < the returned traveled angle
+//     (kNoValue = 15 > a_2 when the ray never crosses the sphere) and
+//     u_lo <= U <= u_hi; r, Ud, Vd, the shift and the emission are disk_hit's
+//     and the sections' above on that r.
+// Per attempt the disk costs one compare (the lane's next crossing against
+// ang') and one ballot; the probe sits in a rarely taken arm behind it.  The
+// cursor is scalars and selects (a per-lane indexed array would go to scratch).
+
+// disk_ray for the adaptive loop: the same crossings; disk_hit's node test
+// `jn[c] < steps` then reads "the ray has a crossing and the loop ran" (jn = 0
+// against steps >= 1 attempts; a ray ended by geodesic_init has steps = 0 and
+// no probe).
+GEO_HD void disk_ray_adaptive(const DiskConsts& d, const PixelConsts& k, float c2x, float c2y, float rho, float rrho,
+                              DiskRay* r) {
+    disk_ray(d, k, c2x, c2y, rho, rrho, r);
+    const uint32_t j = r->jn[0] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+    for (int c = 0; c < kDiskMaxCrossings; ++c) {
+        r->jn[c] = j;
+        r->dn[c] = 0.0f;
+    }
+}
+
+template <int KIND>
+GEO_HD float geodesic_angle_adaptive_disk(const PixelConsts& k, float st, float ct, float rct, const DiskRay& dr,
+                                          uint32_t* steps, float (&Uk)[kDiskMaxCrossings]) {
+    *steps = 0;
+#pragma unroll
+    for (int c = 0; c < kDiskMaxCrossings; ++c) Uk[c] = 0.0f;
+    float U, V, early;
+    if (!geodesic_init<KIND>(k, st, ct, rct, &early, &U, &V)) return early;
+    const StopTest<KIND> stop_at(k);
+    const uint32_t ms = k.max_steps;
+    float h = k.step, ang = 0.0f;
+    float sU, sV, sh, sang, sNU, sNV;
+    GEO_UNSET(sU);
+    GEO_UNSET(sV);
+    GEO_UNSET(sh);
+    GEO_UNSET(sang);
+    GEO_UNSET(sNU);
+    GEO_UNSET(sNV);
+    // the lane's next crossing: slot kc at angle at (+inf: none left)
+    const float none = __builtin_inff();
+    uint32_t kc = 0;
+    float at = dr.jn[0] != 0xFFFFFFFFu ? dr.ak[0] : none;
+    float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f;
+    uint32_t it = 0;
+    uint64_t live = ballot_(true);
+    for (uint32_t n = 1; n <= ms; ++n) {
+        float NU, NV, SE;
+        const float hh = h * h;
+        dp5_step<KIND>(U, V, h, hh, &NU, &NV, &SE);
+        const float err = __builtin_fabsf(SE) * hh;
+        const bool acc = !(err > k.tolU);
+        const uint64_t accm = ballot_(acc);
+        const float angn = ang + h;
+        // (the lanes of `live` as the attempt finds it: the stopping attempt probes)
+        const uint64_t due = ballot_(at < angn) & accm & live;
+        if (due != 0) {
+            if (in_ballot_(due)) {
+                GEO_RARE();
+                do {
+                    const float dl = at - ang;
+                    float wu, wv, se;
+                    dp5_step<KIND>(U, V, dl, dl * dl, &wu, &wv, &se);
+                    u0 = kc == 0u ? wu : u0;
+                    u1 = kc == 1u ? wu : u1;
+                    u2 = kc == 2u ? wu : u2;
+                    ++kc;
+                    at = kc == 1u ? dr.ak[1] : (kc == 2u ? dr.ak[2] : none);
+                } while (at < angn);
+            }
+        }
+        uint64_t hit = accm & stop_at.out_mask(NU) & live;
+        if (hit != 0) hit &= stop_at.exact_refine(NU, NV);
+        if (hit != 0) {
+            if (in_ballot_(hit)) {
+                GEO_RARE();
+                sU = U;
+                sV = V;
+                sh = h;
+                sang = ang;
+                sNU = NU;
+                sNV = NV;
+                it = n;
+            }
+            live &= ~hit;
+            n = live == 0 ? ms : n;
+        }
+        const float grow = (err < k.tolG && h < k.hmax) ? 2.0f : 1.0f;
+        U = acc ? NU : U;
+        V = acc ? NV : V;
+        ang = acc ? angn : ang;
+        h = h * (acc ? grow : 0.5f);
+    }
+    Uk[0] = u0;
+    Uk[1] = u1;
+    Uk[2] = u2;
+    *steps = it != 0 ? it : ms;
+    if (it == 0 || (sNU > k.SU) == (sU > k.SU)) return kNoValue;
+    float ns, wu, wv;
+    if (__builtin_fabsf(sV) > __builtin_fabsf(sNV)) {
+        ns = 0.0f; wu = sU; wv = sV;
+    } else {
+        ns = sh; wu = sNU; wv = sNV;
+    }
+    for (int n = 0; n < kNewtonIters; ++n) {
+        ns = ns - divf_(wu - k.SU, wv);
+        float se;
+        dp5_step<KIND>(sU, sV, ns, ns * ns, &wu, &wv, &se);
+    }
+    return sang + ns;
+}
+
 }  // namespace geo

@@ -611,9 +611,14 @@ static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + si
               "kernel arguments fit 4 KiB");
 template <int KIND>
 static int launch_disk(const RenderArgs& a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh,
-                       const DiskEmitArgs* em, const LaunchPlan& p) {
+                       const DiskEmitArgs* em, bool adaptive, const LaunchPlan& p) {
     FrameBatch<1> fb;
     fb.f[0] = fk;
+    if (adaptive) {  // geo_render_disk_adaptive
+        if (em) return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_emit_kernel<KIND>, fb, d, *em);
+        if (sh) return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_shift_kernel<KIND>, fb, d, *sh);
+        return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_kernel<KIND>, fb, d);
+    }
     if (em) return launch_wave_blocks(a, p, 1, geo_render_disk_emit_kernel<KIND>, fb, d, *em);
     if (sh) return launch_wave_blocks(a, p, 1, geo_render_disk_shift_kernel<KIND>, fb, d, *sh);
     return launch_wave_blocks(a, p, 1, geo_render_disk_kernel<KIND>, fb, d);
@@ -734,6 +739,10 @@ struct RenderCall {
     // any nframes, through the batched ring kernels); every other entry point
     // refuses a batched or supersampled disk frame while the state is on
     bool ring_batch = false;
+    // geo_render_disk_adaptive (GEO_FLAG_DISK scenes in GEO_MODE_ADAPTIVE, one
+    // frame, through the adaptive disk kernels); every other entry point
+    // refuses the disk in that mode
+    bool disk_adaptive = false;
     uint32_t width, height, row0, nrows, band_rows, band_stride;
     uint8_t* out_rgba8;
     uint8_t* out_mask = nullptr;  // (a batch draws colour only)
@@ -771,6 +780,11 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
                           GEO_FLAG_DISK | GEO_FLAG_SS4)) != 0)
         return GEO_EINVAL;
+    // geo_render_disk_adaptive draws GEO_MODE_ADAPTIVE disk scenes only, DISK
+    // with DEFER_STEPS at most (the older calls draw the direct and fan scenes)
+    if (rc.disk_adaptive &&
+        (scene->mode != GEO_MODE_ADAPTIVE || (scene->flags & ~GEO_FLAG_DEFER_STEPS) != GEO_FLAG_DISK))
+        return GEO_EINVAL;
     // GEO_FLAG_SS4 (every rule here, where the bit was refused as an unknown
     // one before: a call that breaks an older rule too keeps its status): the
     // one-frame entry points (the ones that draw a disk frame alone) and
@@ -790,7 +804,7 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // GEO_FLAG_DISK: the one-frame entry points, geo_render_disk_batch and (with SS4) geo_render_ss_batch, direct
     // mode, DEFER_STEPS at most
     w.disk = (scene->flags & GEO_FLAG_DISK) != 0;
-    if (w.disk && (!rc.allow_disk || scene->mode != GEO_MODE_DIRECT ||
+    if (w.disk && (!rc.allow_disk || scene->mode != (rc.disk_adaptive ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
                    (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0))
         return GEO_EINVAL;
     // geo_render_disk_batch draws disk scenes only, and colour only: an armed
@@ -848,6 +862,9 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
         // shading: circular timelike orbits down to the inner edge
         if ((c->shift_set || c->emit_set) && scene->rs > 0.0f && !(c->disk.r_in > 1.5f * scene->rs))
             return GEO_EINVAL;
+        // geo_render_disk_adaptive with geo_set_disk_ring_f64 on and a capture
+        // orbit to draw: the frame would come out without its band
+        if (rc.disk_adaptive && w.disk_ring) return GEO_EINVAL;
     }
     return GEO_OK;
 }
@@ -1087,7 +1104,7 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
             return launch_disk_ring<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
                                                            w.emit ? &em : nullptr, band_k, w.p);
         return launch_disk<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
-                                                  w.emit ? &em : nullptr, w.p);
+                                                  w.emit ? &em : nullptr, w.adaptive, w.p);
     });
 }
 
@@ -1684,6 +1701,29 @@ int geo_render_band_set(geo_ctx* c, const geo_frame* frame, const geo_scene* sce
     RenderCall rc = render_call(frame, scene, width, height, row0, nbands * band_rows, band_rows, row_stride,
                                 out_rgba8, steps_total, stream);
     rc.allow_disk = true;
+    rc.out_mask = out_mask;
+    rc.out_uv = out_uv;
+    rc.out_steps = out_steps;
+    return render_impl(c, rc);
+}
+
+int geo_render_disk_adaptive(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
+                             uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride, uint32_t nbands,
+                             uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+                             unsigned long long* steps_total, void* stream) {
+    // a row range is the one-band case: any number of rows, as one band that
+    // covers them all (geo_render_rows' mapping; row_stride is not read)
+    const bool rows = nbands == 1 && band_rows != 0 && band_rows <= (1u << 20) && width != 0 && height != 0 &&
+                      width <= (1u << 20) && height <= (1u << 20) && row0 < height;
+    if (!c || !frame || !scene || !out_rgba8 ||
+        (!rows && !band_set_ok(width, height, band_rows, row0, row_stride, nbands)))
+        return invalid_call(c);
+    RenderCall rc = nbands == 1 ? render_call(frame, scene, width, height, row0, band_rows, 1u << 21, 1u << 21,
+                                              out_rgba8, steps_total, stream)
+                                : render_call(frame, scene, width, height, row0, nbands * band_rows, band_rows,
+                                              row_stride, out_rgba8, steps_total, stream);
+    rc.allow_disk = true;
+    rc.disk_adaptive = true;
     rc.out_mask = out_mask;
     rc.out_uv = out_uv;
     rc.out_steps = out_steps;

@@ -654,7 +654,8 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
 
 // ---- GEO_FLAG_DISK: the thin accretion disk (geo_disk.h) ----------------
 // The disk renders are kernels of their own beside geo_render_kernel, whose
-// instantiations carry no disk branch, argument or register: GEO_MODE_DIRECT,
+// instantiations carry no disk branch, argument or register: GEO_MODE_DIRECT
+// (GEO_MODE_ADAPTIVE in the kernels of geo_render_disk_adaptive),
 // level-0 sampler, one wave per workgroup on the 1-D grid of the plain
 // direct-mode render (wave_blocks), the same tile mapping, step counting and
 // tile-cost recording.  The argument structs come first, then the ring
@@ -977,7 +978,7 @@ struct DiskEmitBatchArgs {
 // source and calls wave_block_body, which holds what they share: the tile
 // mapping, the camera ray, geo::disk_ray and geo::geodesic_angle_disk, the sky
 // sample, the disk texture quad, the shading call, the SS4 resolve, and the
-// step-slot and tile-cost epilogue.  It varies along four properties of the
+// step-slot and tile-cost epilogue.  It varies along five properties of the
 // render, not of the caller:
 //   SHADE  what is shaded: the sky alone (pixel_lambda), or the disk plain,
 //          shifted or with its emission (geo::disk_shade, _shift, _emit)
@@ -987,6 +988,10 @@ struct DiskEmitBatchArgs {
 //   SIDE   the per-pixel side outputs of the one-frame one-sample renders
 //          (mask, uv, steps, hits, g, q; the sky UV also where only a.out_uv
 //          asks for it); every other render is colour only
+//   MODE   the integrator: GEO_MODE_DIRECT (geo::geodesic_angle_disk), or
+//          GEO_MODE_ADAPTIVE (geo::geodesic_angle_adaptive_disk, the one-frame
+//          one-sample disk renders of geo_render_disk_adaptive; a tile's cost
+//          is then in attempts)
 //   SRC    the frame source: what frame z of the launch reads its camera,
 //          scene, disk, texture, shift or emission constants and ramp from,
 //          where its output starts and whether it records tile costs, one
@@ -1093,9 +1098,11 @@ struct DiskBatchFrame {
 
 // out_width (SS): the output's pitch in pixels; RenderArgs then describes the
 // sample frame.
-template <int KIND, Shade SHADE, bool SS, bool SIDE, typename SRC>
+template <int KIND, Shade SHADE, bool SS, bool SIDE, int MODE = GEO_MODE_DIRECT, typename SRC>
 __device__ __forceinline__ void wave_block_body(const RenderArgs& a, const SRC& src, uint32_t out_width) {
     static_assert(!(SS && SIDE) && !(SIDE && SHADE == Shade::kSky), "side outputs: the one-sample disk renders'");
+    static_assert(MODE == GEO_MODE_DIRECT || (MODE == GEO_MODE_ADAPTIVE && SHADE != Shade::kSky && !SS && SIDE),
+                  "the adaptive integrator: the one-frame one-sample disk renders'");
     // geo_render_kernel's WB mapping: workgroup L draws wave `wave` of the tile
     // at dispatch position pos.  The padding of the last group (a whole
     // workgroup) leaves here: the body's only early exit, and a wave-uniform
@@ -1156,9 +1163,15 @@ __device__ __forceinline__ void wave_block_body(const RenderArgs& a, const SRC& 
         } else {
             const auto& dk = src.disk();
             geo::DiskRay dr;
-            geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
             float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            float ang;
+            if constexpr (MODE == GEO_MODE_ADAPTIVE) {
+                geo::disk_ray_adaptive(dk, k, c2x, c2y, ct, rct, &dr);
+                ang = geo::geodesic_angle_adaptive_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            } else {
+                geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+                ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            }
             const float lam = geo::kPi2 - ang;
             const bool bh = lam < geo::kBlackHoleLambda;
             float U = 0.0f, V = 0.0f;
@@ -1244,6 +1257,31 @@ template <int KIND>
 __global__ __launch_bounds__(64) void geo_render_disk_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
                                                                   const DiskArgs d, const DiskEmitArgs em) {
     wave_block_body<KIND, Shade::kDiskEmit, false, true>(a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, d, em}, 0u);
+}
+
+// geo_render_disk_adaptive: the same three renders with the adaptive
+// integrator (the argument layouts are the direct kernels').
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_adaptive_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                      const DiskArgs d) {
+    wave_block_body<KIND, Shade::kDisk, false, true, GEO_MODE_ADAPTIVE>(
+        a, DiskFrame<NoArgs>{{a, fb, 0u}, d, NoArgs{}}, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_adaptive_shift_kernel(const RenderArgs a,
+                                                                            const FrameBatch<1> fb, const DiskArgs d,
+                                                                            const DiskShiftArgs sh) {
+    wave_block_body<KIND, Shade::kDiskShift, false, true, GEO_MODE_ADAPTIVE>(
+        a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, d, sh}, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_adaptive_emit_kernel(const RenderArgs a,
+                                                                           const FrameBatch<1> fb, const DiskArgs d,
+                                                                           const DiskEmitArgs em) {
+    wave_block_body<KIND, Shade::kDiskEmit, false, true, GEO_MODE_ADAPTIVE>(
+        a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, d, em}, 0u);
 }
 
 // geo_render_disk_batch.  SHIFT: the shaded batch (geo_set_disk_shift).

@@ -85,6 +85,20 @@ counts as a gain where it is faster than the one-frame side by more than twice
 that side's alternation spread.
 
   python tools/bench_disk.py --batch 8 --ring [--out profiles/disk_ring_batch_bench_cfg3.json]
+
+--adaptive measures the adaptive disk frame (geo_render_disk_adaptive) against
+the plain GEO_MODE_ADAPTIVE frame of the same scene: config 3's scene with the
+disk 1.6..2.2 rs at config 5's mode, step and tol, by --ring's method, each
+kind on its own context: --alternations (5) times --n (30) event-timed
+dispatches of each kind in blocks, after --settle (4) alternations of the same
+form that are reported apart, --sessions (2) sessions.  The direct disk frame
+and the direct plain frame run beside them in the same alternations, for
+orientation.  Per session it reports the medians over the alternations, the
+adaptive disk frame over the plain adaptive one (the surplus), the plain
+side's spread ((max - min) / median of its alternation medians) and whether
+the surplus lies beyond twice that spread.  One JSON object.
+
+  python tools/bench_disk.py --adaptive [--out profiles/disk_adaptive_bench.json]
 """
 from __future__ import annotations
 
@@ -107,6 +121,9 @@ def main():
     p.add_argument("--ring", action="store_true",
                    help="time the disk frame with geo_set_disk_ring_f64 on against off, and the plain frame with and "
                         "without GEO_FLAG_RING_F64, in alternating blocks")
+    p.add_argument("--adaptive", action="store_true",
+                   help="time the adaptive disk frame (geo_render_disk_adaptive) against the plain adaptive frame, in "
+                        "alternating blocks")
     p.add_argument("--alternations", type=int, default=5, help="with --emission: blocks of --n renders of each kind")
     p.add_argument("--settle", type=int, default=4,
                    help="with --emission: alternations run first in the timed form, reported apart and not counted")
@@ -119,8 +136,10 @@ def main():
                         "batch its last (default: the other way round)")
     p.add_argument("--out")
     args = p.parse_args()
+    if args.adaptive and (args.batch or args.ring or args.emission or args.shift):
+        raise SystemExit("--adaptive goes alone")
     if not args.out:
-        name = "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
+        name = "disk_adaptive_bench.json" if args.adaptive else "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
             args.ring) else "disk_emission_batch_bench_cfg3.json" if (
             args.batch and args.emission) else (
             "disk_batch_bench_cfg3.json") if args.batch else (
@@ -129,6 +148,8 @@ def main():
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.adaptive:
+        return adaptive_main(args)
     if args.batch and args.ring:
         return ring_batch_main(args)
     if args.ring:
@@ -416,6 +437,125 @@ def ring_main(args):
         "timing": "geo_time_next_render event pairs on each kernel dispatch; blocks of n renders of the disk frame with "
                   "the state off, with it on, the plain frame and the plain GEO_FLAG_RING_F64 frame alternate in one "
                   "process, each kind on its own context; spread = (max - min) / median of a kind's alternation medians",
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+def adaptive_session(args, cfg, frame, scenes, sky, tex):
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent
+
+    W, H = cfg.width, cfg.height
+    r_in, r_out = 1.6 * cfg.rs, 2.2 * cfg.rs
+    # (each kind on its own context: the learned dispatch order is kept per context)
+    ctxs = {}
+    for kind in scenes:
+        c = g.Context(0)
+        c.set_sky(sky)
+        if kind.startswith("disk"):
+            c.set_disk(tex, r_in, r_out)
+        ctxs[kind] = c
+    dev = torch.device("cuda:0")
+    out = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)
+
+    def run(kind):
+        if kind == "disk_adaptive":
+            ctxs[kind].render_disk_adaptive(frame, scenes[kind], W, H, H, 0, H, 1, out)
+        else:
+            ctxs[kind].render_rows(frame, scenes[kind], W, H, 0, H, out)
+
+    for _ in range(args.warmup):
+        for kind in ctxs:
+            run(kind)
+    torch.cuda.synchronize()
+    blocks, settling = [], []
+    for alt in range(args.settle + args.alternations):
+        med = {}
+        for kind, c in ctxs.items():
+            ev = []
+            for _ in range(args.n):
+                a, b = HipEvent(), HipEvent()
+                c.time_next_render(a, b)
+                run(kind)
+                ev.append((a, b))
+            torch.cuda.synchronize()
+            ms = np.array([a.elapsed_time(b) for a, b in ev])
+            med[kind + "_ms_median"] = float(np.median(ms))
+            med[kind + "_ms_min"] = float(ms.min())
+            med[kind + "_ms_iqr"] = float(np.subtract(*np.percentile(ms, [75, 25])))
+        med["disk_adaptive_over_plain_adaptive"] = med["disk_adaptive_ms_median"] / med["plain_adaptive_ms_median"]
+        med["disk_direct_over_plain_direct"] = med["disk_direct_ms_median"] / med["plain_direct_ms_median"]
+        (settling if alt < args.settle else blocks).append(med)
+    # what the adaptive disk frame draws (untimed): its hits, and both adaptive frames' attempts
+    hits = torch.zeros(W * H * 6, dtype=torch.float32, device=dev)
+    tot_d = torch.zeros(1, dtype=torch.int64, device=dev)
+    tot_p = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctxs["disk_adaptive"].disk_hits_next_render(hits)
+    ctxs["disk_adaptive"].render_disk_adaptive(frame, scenes["disk_adaptive"], W, H, H, 0, H, 1, out, None, None, None,
+                                               tot_d)
+    ctxs["plain_adaptive"].render_rows(frame, scenes["plain_adaptive"], W, H, 0, H, out, None, None, None, tot_p)
+    torch.cuda.synchronize()
+    hv = hits.view(H, W, 3, 2)[..., 0] > 0
+    for c in ctxs.values():
+        c.close()
+    m = {k: np.array([b[k + "_ms_median"] for b in blocks]) for k in ctxs}
+    spread = {k: float((m[k].max() - m[k].min()) / np.median(m[k])) for k in ("plain_adaptive", "plain_direct")}
+    ratio = float(np.median(m["disk_adaptive"]) / np.median(m["plain_adaptive"]))
+    return {
+        "settling_alternations_not_counted": settling, "alternations": blocks,
+        **{k + "_ms_median": float(np.median(v)) for k, v in m.items()},
+        "disk_adaptive_over_plain_adaptive": ratio,
+        "disk_adaptive_over_plain_adaptive_min": float(min(b["disk_adaptive_over_plain_adaptive"] for b in blocks)),
+        "disk_adaptive_over_plain_adaptive_max": float(max(b["disk_adaptive_over_plain_adaptive"] for b in blocks)),
+        "surplus_ms_per_frame": float(np.median(m["disk_adaptive"]) - np.median(m["plain_adaptive"])),
+        "plain_adaptive_alternation_spread": spread["plain_adaptive"],
+        "surplus_beyond_twice_the_spread": bool(abs(ratio - 1.0) > 2.0 * spread["plain_adaptive"]),
+        "disk_direct_over_plain_direct": float(np.median(m["disk_direct"]) / np.median(m["plain_direct"])),
+        "plain_direct_alternation_spread": spread["plain_direct"],
+        "hit_pixels_per_slot": [int(hv[..., k].sum()) for k in range(3)],
+        "attempts_total_disk_adaptive": int(tot_d.item()), "attempts_total_plain_adaptive": int(tot_p.item()),
+    }
+
+
+def adaptive_main(args):
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg, cfg5 = CONFIGS["cfg3_4k"], CONFIGS["cfg5_8k_adaptive"]
+    obs = g.Observer(cfg.rs, cfg.fov, cfg.width, cfg.height)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    r = obs.get_radial_position()
+    A, D = _lib.GEO_MODE_ADAPTIVE, _lib.GEO_MODE_DIRECT
+    scenes = {
+        "plain_adaptive": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg5.step, cfg5.max_steps, A, 0, cfg5.tol),
+        "disk_adaptive": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg5.step, cfg5.max_steps, A, _lib.GEO_FLAG_DISK, cfg5.tol),
+        "plain_direct": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg.step, cfg.max_steps, D, 0),
+        "disk_direct": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg.step, cfg.max_steps, D, _lib.GEO_FLAG_DISK),
+    }
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    res = {
+        "config": "cfg3_4k's scene at cfg5_8k_adaptive's mode, step and tol", "width": cfg.width, "height": cfg.height,
+        "step": cfg5.step, "tol": cfg5.tol, "max_steps": cfg5.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs],
+        "n": args.n, "alternations": args.alternations, "settle": args.settle, "warmup": args.warmup,
+        "timing": "geo_time_next_render event pairs on each kernel dispatch; blocks of n renders of the plain adaptive "
+                  "frame, the adaptive disk frame, the plain direct frame and the direct disk frame alternate in one "
+                  "process, each kind on its own context; spread = (max - min) / median of a kind's alternation "
+                  "medians; a surplus is a figure only beyond twice the plain adaptive side's spread",
+        "sessions": [adaptive_session(args, cfg, frame, scenes, sky, tex) for _ in range(args.sessions)],
     }
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -9,7 +9,7 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
         [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
-        [--disk-ring-f64]
+        [--disk-ring-f64] [--adaptive [--tol T]]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -27,6 +27,10 @@ it takes the place of --disk-shift and works with --cpu and --ss.
 --disk-ring-f64 takes the pixels of the capture band through the f64 path
 (geo_set_disk_ring_f64: the third image's radii and colours to the disk's
 accuracy bar), on the GPU or with --cpu, not with --ss.
+--adaptive draws the disk frame with the error-controlled integrator
+(GEO_MODE_ADAPTIVE through geo_render_disk_adaptive, --tol its tolerance in u,
+0 = the default 1e-6), unshaded, with --disk-shift or with --disk-emission, on
+the GPU or with --cpu; not with --ss or --disk-ring-f64.
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -65,7 +69,8 @@ def disk_frame(args):
     obs.set_camera(*args.camera)
     frame = obs.calc_transformation_pipeline()
     scene = g.make_scene(1.0, 50.0, obs.get_radial_position(), math.pi / 100, 2048,
-                         flags=_lib.GEO_FLAG_DISK | (_lib.GEO_FLAG_SS4 if args.ss else 0))
+                         _lib.GEO_MODE_ADAPTIVE if args.adaptive else _lib.GEO_MODE_DIRECT,
+                         _lib.GEO_FLAG_DISK | (_lib.GEO_FLAG_SS4 if args.ss else 0), args.tol)
     sky = imageio.load_texture(args.sky) if args.sky else make_sky("equirect", (2048, 1024))
     tex = make_disk_texture((1024, 128))
     r_in, r_out = args.disk
@@ -81,7 +86,18 @@ def disk_frame(args):
         base = [vp, vp, vp, u32, u32, vp, u32, u32, u32, u32, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, u32,
                 u32, vp]
         ring = 1 if args.disk_ring_f64 else 0
-        if emission is not None:
+        if args.adaptive:
+            name = "geo_render_cpu_disk_adaptive"
+            shift = None
+            if args.disk_shift:
+                shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
+            lib.geo_render_cpu_disk_adaptive.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_adaptive.argtypes = base + [vp, vp, u32, vp, vp, vp]
+            rc = lib.geo_render_cpu_disk_adaptive(
+                *common, ctypes.addressof(emission) if emission is not None else None,
+                ramp.ctypes.data if ramp is not None else None, ramp.shape[0] if ramp is not None else 0, None, None,
+                ctypes.addressof(shift) if shift else None)
+        elif emission is not None:
             name = "geo_render_cpu_disk_ring_f64"
             lib.geo_render_cpu_disk_ring_f64.restype = ctypes.c_int
             lib.geo_render_cpu_disk_ring_f64.argtypes = base + [vp, vp, u32, vp, vp, ctypes.c_int]
@@ -111,7 +127,10 @@ def disk_frame(args):
         if args.disk_ring_f64:
             ctx.set_disk_ring_f64(True)
         rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
-        ctx.render_rows(frame, scene, w, h, 0, h, rgba)
+        if args.adaptive:
+            ctx.render_disk_adaptive(frame, scene, w, h, h, 0, h, 1, rgba)
+        else:
+            ctx.render_rows(frame, scene, w, h, 0, h, rgba)
     if args.out.endswith(".ppm"):
         imageio.save_ppm(args.out, rgba, w, h)
     elif args.out.endswith((".jpg", ".jpeg")):
@@ -120,7 +139,8 @@ def disk_frame(args):
         Image.fromarray(imageio.frame_to_host(rgba, w, h)[..., :3].copy(), "RGB").save(args.out, quality=88)
     else:
         imageio.save_png(args.out, rgba, w, h)
-    print(f"wrote {args.out} ({w}x{h}{', 2x2 supersampled' if args.ss else ''}, thin disk {r_in}..{r_out}, "
+    print(f"wrote {args.out} ({w}x{h}{', 2x2 supersampled' if args.ss else ''}"
+          f"{', adaptive' if args.adaptive else ''}, thin disk {r_in}..{r_out}, "
           f"{'CPU path' if args.cpu else 'GPU'})")
 
 
@@ -150,6 +170,10 @@ def main():
     p.add_argument("--disk-spin", type=int, choices=(1, -1), default=1, help="with --disk-emission")
     p.add_argument("--disk-ring-f64", action="store_true",
                    help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); not with --ss")
+    p.add_argument("--adaptive", action="store_true",
+                   help="with --disk: the error-controlled integrator (geo_render_disk_adaptive); not with --ss or "
+                        "--disk-ring-f64")
+    p.add_argument("--tol", type=float, default=0.0, help="with --adaptive: the tolerance in u (0 = 1e-6)")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
     p.add_argument("--pos", type=float, nargs=3, default=(2.4, 0.0, 0.7), help="with --disk: observer position")
@@ -158,6 +182,10 @@ def main():
     args = p.parse_args()
     if args.disk_ring_f64 and (not args.disk or args.ss):
         p.error("--disk-ring-f64 goes with --disk and without --ss (a supersampled disk frame refuses the state)")
+    if args.adaptive and (not args.disk or args.ss or args.disk_ring_f64):
+        p.error("--adaptive goes with --disk and without --ss and --disk-ring-f64 (the adaptive disk has neither)")
+    if args.tol != 0.0 and not args.adaptive:
+        p.error("--tol goes with --adaptive")
     if args.disk:
         return disk_frame(args)
     if args.ss:
