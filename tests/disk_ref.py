@@ -14,9 +14,23 @@ numpy, f64, no code shared with csrc/geo_disk.h:
   sphere, u <= 1/sphere_r; before the horizon, u > 1/rs with u' > 0; before
   the budget max_steps * step) and r_in <= 1/u(a_k) <= r_out.
 
-It assumes an observer inside the sky sphere and outside the photon sphere
-(r_obs > 3 rs/2, or rs = 0), where none of the reference's pre-filters
-(sphere_ray_tracer.rs:106-119) ends a ray before the loop.
+It holds for every observer between the horizon and the sky sphere (or
+rs = 0) as long as the disk lies outside the photon sphere, r_in > 1.5 rs,
+which GEO_FLAG_DISK's scenes in tests/fuzz_disk_scenes.py keep.  Inside the
+photon sphere the reference's pre-filters (sphere_ray_tracer.rs:106-119) end
+some rays before the loop: those that start inwards (they fall into the
+horizon: the potential has no barrier below 1.5 rs) and those that start
+outwards with b > b_c (they turn back below the photon sphere).  Either kind
+stays at r < 1.5 rs < r_in, so no crossing of it is a hit on either side: the
+filters cannot change a hit, and the trace needs none of them.
+tests/disk_truth.py runs the trace over the fuzzed observers (inside the
+photon sphere, under a small sky sphere, tilted and edge-on disks) and counts
+no hit/no-hit disagreement off the annulus' edges.
+
+trace also returns `cond` = hypot(A, B) of a_0 = atan2(-B, A), the length of
+the disk normal's projection onto the ray's plane: a_0, and with it every
+crossing's radius and azimuth, is conditioned like 1/cond (cond -> 0 where the
+ray's plane nearly contains the disk's plane).
 
 Tolerances (the scheme of f64_bar.py's K_AMP and A_DIR): the CPU path
 (geo_render_cpu_disk, bit-equal to the kernel) was measured against this
@@ -62,12 +76,13 @@ def _m3(m16):
     return a[:3, :3], a
 
 
-def camera(frame, width, height):
+def camera(frame, width, height, k=None):
     """Per pixel, in f64: the unit direction c2 (h, w, 3) in the black-hole-
-    central frame (shader.wgsl:60-75)."""
+    central frame (shader.wgsl:60-75).  k: the frame's own aberration factor
+    unless given (trace's mutation)."""
     m0_3, m0 = _m3(frame.display_to_movement)
     m1_3, _ = _m3(frame.movement_to_central)
-    k = float(frame.psi_factor_and_position[0])
+    k = float(frame.psi_factor_and_position[0]) if k is None else k
     px = np.arange(width, dtype=np.float64)[None, :]
     py = np.arange(height, dtype=np.float64)[:, None]
     nx = (2.0 * px + 1.0 - width) / width + 0.0 * py
@@ -109,13 +124,26 @@ def _rk4(u, v, h, c):
     return u + h / 6.0 * (k1u + 2 * k2u + 2 * k3u + k4u), v + h / 6.0 * (k1v + 2 * k2v + 2 * k3v + k4v)
 
 
-def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis=(1.0, 0.0, 0.0), sub=8):
+# wrong traces for tests/disk_truth.py's mutation test: the aberration dropped (k = 0),
+# E = 1 in the initial slope, flat geodesics in a curved scene (c = 0), the azimuth's sense
+# flipped, the slots shifted by one (slot k holds crossing k + 1), and the budget ignored
+# (in the crossing condition and in t_end)
+MUTATIONS = ("no_aberration", "slope_e1", "flat_c", "az_flipped", "slot_shift", "budget_ignored")
+
+
+def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis=(1.0, 0.0, 0.0), sub=8,
+          mutation=None):
     """dict: hit (h, w, 3) bool, r, az (h, w, 3) f64 (radius and azimuth in
     turns in [0, 1) of each crossing, nan where the ray never got there), x
-    (h, w) = |b/b_c - 1| (inf for rs = 0), theta (h, w)."""
+    (h, w) = |b/b_c - 1| (inf for rs = 0), theta (h, w), cond (h, w) = hypot(A, B)
+    of a_0 = atan2(-B, A) (the docstring's conditioning of a_0).
+
+    mutation: None, or one of MUTATIONS: a deliberately wrong trace that
+    tests/disk_truth.py's checks must refuse (nothing else reads it)."""
+    assert mutation is None or mutation in MUTATIONS, mutation
     rs, R, r0 = float(scene.rs), float(scene.sphere_r), float(scene.r_obs)
     step, budget = float(scene.step), int(scene.max_steps)
-    c2 = camera(frame, width, height)
+    c2 = camera(frame, width, height, k=0.0 if mutation == "no_aberration" else None)
     rho = np.hypot(c2[..., 0], c2[..., 1])
     st = np.clip(c2[..., 2], -1.0, 1.0)
     theta = np.arctan2(st, rho)
@@ -129,11 +157,15 @@ def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis
     a0 = np.where(a0 <= 0.0, math.pi, a0)  # in (0, pi]
     E = math.sqrt(1.0 - rs / r0) if rs > 0.0 else 1.0
     u = np.full(rho.shape, 1.0 / r0)
-    v = (E / r0) * st / rho
-    c = 1.5 * rs
+    v = ((1.0 if mutation == "slope_e1" else E) / r0) * st / rho
+    c = 0.0 if mutation == "flat_c" else 1.5 * rs
     su, hu = 1.0 / R, (1.0 / rs if rs > 0.0 else math.inf)
     h = step / sub
     ak = a0[..., None] + math.pi * np.arange(MAX_CROSSINGS)[None, None, :]
+    if mutation == "slot_shift":
+        ak = ak + math.pi
+    if mutation == "budget_ignored":
+        budget = 2 ** 30
     t_end = min(float(ak.max()) + step, budget * step)
     nsub = int(math.ceil(t_end / h))
     alive = np.ones(rho.shape, dtype=bool)
@@ -160,12 +192,12 @@ def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis
     sa, ca = np.sin(ak), np.cos(ak)
     X = sa * (Ex[0] * cphi + Ex[1] * sphi)[..., None] + ca * Ex[2]
     Y = sa * (Ey[0] * cphi + Ey[1] * sphi)[..., None] + ca * Ey[2]
-    az = np.mod(np.arctan2(Y, X) / (2.0 * math.pi), 1.0)
+    az = np.mod(np.arctan2(-Y if mutation == "az_flipped" else Y, X) / (2.0 * math.pi), 1.0)
     if rs > 0.0 and r0 > rs:
         x = np.abs(r0 * np.cos(theta) / E / (1.5 * math.sqrt(3.0) * rs) - 1.0)
     else:
         x = np.full(theta.shape, np.inf)
-    return dict(hit=hit, r=r, az=az, x=x, theta=theta)
+    return dict(hit=hit, r=r, az=az, x=x, theta=theta, cond=np.hypot(A, B))
 
 
 def az_err(a, b):

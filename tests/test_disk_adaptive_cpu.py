@@ -32,7 +32,11 @@ What a host build cannot see: it has one lane per wave, so `live` is all or
 nothing; the GPU tests run the kernels' waves against this path.
 
 Then the renders: the plain outputs against geo_render_cpu's adaptive render,
-the hits against the independent f64 answer tests/disk_ref.py and against
+the hits against the independent f64 answer tests/disk_ref.py on poses A and B
+(the direct mode's bars TOL_R and TOL_AZ were shown to hold at the default tol
+on those two poses only; next to the capture orbit, 0.02 <= |b/b_c - 1| < 0.05,
+fuzzed scenes reach 1.95e-4 in radius, which tests/disk_truth.py's model of the
+adaptive mode carries and include/geo/geo.h documents) and against
 straight lines in flat space, the shading against disk_shift_ref and
 disk_emission_ref on the returned radii, and the argument rules.
 """
@@ -258,7 +262,9 @@ def curved(cpu):
 @pytest.mark.parametrize("name", list(T.CURVED))
 def test_curved_space_against_disk_ref(curved, name):
     """The direct mode's committed bars TOL_R and TOL_AZ, its band BAND_X and
-    its cap on the excluded share, at the adaptive mode's default tol."""
+    its cap on the excluded share, at the adaptive mode's default tol, on poses
+    A and B (the fuzzed scenes and their wider bar next to the band:
+    tests/test_disk_truth_cpu.py)."""
     a, p, ref, r_in, r_out = curved[name][:5]
     s = D.compare(a["hits"], ref, r_in, r_out)
     shadow = p["mask"] == 1
