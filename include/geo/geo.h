@@ -67,7 +67,9 @@ extern "C" {
                                    announced by GEO_HAS_DISK_RING_BATCH:
                                    geo_render_disk_ring_batch;
                                    announced by GEO_HAS_DISK_ADAPTIVE:
-                                   geo_render_disk_adaptive) */
+                                   geo_render_disk_adaptive;
+                                   announced by GEO_HAS_DISK_ADAPTIVE_BATCH:
+                                   geo_render_disk_adaptive_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -78,6 +80,7 @@ extern "C" {
 #define GEO_HAS_DISK_RING_F64 1
 #define GEO_HAS_DISK_RING_BATCH 1
 #define GEO_HAS_DISK_ADAPTIVE 1
+#define GEO_HAS_DISK_ADAPTIVE_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -154,8 +157,9 @@ typedef enum geo_status {
                                    one launch (the multi-GPU pipeline's batches, a moving
                                    observer's frames); geo_render_band_set_frames / _batch
                                    refuse the flag.  GEO_MODE_DIRECT (GEO_MODE_ADAPTIVE
-                                   through geo_render_disk_adaptive alone, whose comment
-                                   states the crossing rule of that mode),
+                                   through geo_render_disk_adaptive, whose comment states
+                                   the crossing rule of that mode, and
+                                   geo_render_disk_adaptive_batch alone),
                                    with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
                                    and rs < r_in; r_out < sphere_r and r_obs < sphere_r
                                    (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
@@ -188,7 +192,9 @@ typedef enum geo_status {
                                    geo_render_rows / _bands / _band_set, GEO_MODE_DIRECT, the
                                    level-0 sampler, with GEO_FLAG_DISK (shaded by
                                    geo_set_disk_shift or not) and GEO_FLAG_DEFER_STEPS at most.
-                                   GEO_EINVAL with GEO_MODE_FAN, GEO_MODE_ADAPTIVE,
+                                   GEO_EINVAL with GEO_MODE_FAN, GEO_MODE_ADAPTIVE (but
+                                   through geo_render_disk_adaptive_batch, the only call
+                                   that supersamples an adaptive disk frame),
                                    GEO_FLAG_MIPS, GEO_FLAG_COMPOSITE or GEO_FLAG_RING_F64,
                                    through geo_render_band_set_frames / _batch and
                                    geo_render_disk_batch, and where 2 width or 2 height
@@ -705,14 +711,60 @@ int geo_render_disk_ring_batch(geo_ctx* ctx, const geo_frame* frames, const geo_
  * launches nothing, writes nothing and consumes the armed buffers and the
  * timing pair.  geo_time_next_render, geo_set_dispatch (the learned order has
  * a grid key of its own; a tile's cost is in attempts) and geo_set_tile_order
- * work as for the one-frame direct render.  Not in this ABI: batched adaptive
- * disk frames and the multi-GPU pipeline, GEO_FLAG_SS4 and the f64 capture
- * band with the adaptive disk.  Every older call keeps every refusal it has.
- * Asynchronous on `stream`. */
+ * work as for the one-frame direct render.  Batched adaptive disk frames, the
+ * multi-GPU pipeline's and GEO_FLAG_SS4 with the adaptive disk go through
+ * geo_render_disk_adaptive_batch (this call keeps refusing the flag).  Not in
+ * this ABI: the f64 capture band with the adaptive disk.  Every older call
+ * keeps every refusal it has.  Asynchronous on `stream`. */
 int geo_render_disk_adaptive(geo_ctx* ctx, const geo_frame* frame, const geo_scene* scene, uint32_t width,
                              uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
                              uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
                              uint32_t* out_steps, unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for the thin disk in GEO_MODE_ADAPTIVE
+ * (GEO_HAS_DISK_ADAPTIVE_BATCH): nframes (1 .. GEO_MAX_BATCH_FRAMES)
+ * GEO_MODE_ADAPTIVE | GEO_FLAG_DISK frames of the context's disk in ONE render
+ * launch, scenes[f] for frames[f], the band-set layout and the
+ * out_frame_stride rules of the other batches.  The shading is what the
+ * context has set: none, geo_set_disk_shift, or geo_set_disk_emission (which
+ * takes the shift's place, as everywhere else).
+ * One-sample frames: frame f's bytes are those of geo_render_disk_adaptive with
+ * frames[f], scenes[f], the same layout and the same context state, bit for
+ * bit, and so geo_render_cpu_disk_adaptive's; steps_total (or the deferred
+ * accumulator) is the sum of those renders' attempts.
+ * GEO_FLAG_SS4 on every scene or on none (width, height, rows and bands are
+ * then in output pixels, with geo_render_ss_batch's size limits of 2^19).  No
+ * one-frame supersampled adaptive render exists (geo_render_disk_adaptive keeps
+ * refusing the flag), so the flag's own definition fixes frame f: output pixel
+ * (x, y) is the per-channel (s00 + s01 + s10 + s11 + 2) >> 2 of pixels
+ * (2x + i, 2y + j) of the one-sample geo_render_disk_adaptive render at
+ * 2 width x 2 height with the same uniform and scene; the steps are those of
+ * every sample over sample rows 2r, 2r + 1.
+ * Every scene carries GEO_MODE_ADAPTIVE and GEO_FLAG_DISK, with
+ * GEO_FLAG_DEFER_STEPS and GEO_FLAG_SS4 at most, and tol under the adaptive
+ * mode's rules; the scenes may differ in r_obs only (tol, step and the budget
+ * are equal across the batch) and share the integration kind.
+ * geo_render_disk_adaptive's disk rules hold for every frame's scene, r_in >
+ * 1.5 rs with a shift or an emission set included; anything else is
+ * GEO_EINVAL.  GEO_ESTATE when no sky or no disk is set.  GEO_EINVAL while
+ * geo_set_disk_ring_f64 is on and rs > 0: the frames would come out without
+ * their band (with rs == 0 the state is ignored).  Colour only: a buffer armed
+ * by geo_disk_hits_next_render, geo_disk_shift_next_render or
+ * geo_disk_emission_next_render is consumed and the call returns GEO_EINVAL.
+ * A refused call launches nothing, writes nothing and drops the timing pair;
+ * ctx, frames, scenes or out_rgba8 NULL and nframes out of range are refused
+ * before any device work.  geo_time_next_render, geo_set_dispatch and
+ * geo_set_tile_order work as for the other batches (frame 0 records the tile
+ * costs, a tile's cost being in attempts; the learned order's key holds the
+ * mode beside the disk, SS and emission bits; under GEO_FLAG_SS4 the grid is
+ * the sample frame's).  Not in this ABI: per-pixel outputs from a batch, and
+ * the f64 capture band with the adaptive disk.  Every older call keeps every
+ * refusal it has.  One scene for every frame: pass copies.  Asynchronous on
+ * `stream`. */
+int geo_render_disk_adaptive_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                                   uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                                   uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                                   unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

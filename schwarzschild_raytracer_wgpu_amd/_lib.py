@@ -43,6 +43,7 @@ GEO_HAS_DISK_EMISSION_BATCH = 1  # geo_render_emission_batch
 GEO_HAS_DISK_RING_F64 = 1  # geo_set_disk_ring_f64
 GEO_HAS_DISK_RING_BATCH = 1  # geo_render_disk_ring_batch
 GEO_HAS_DISK_ADAPTIVE = 1  # geo_render_disk_adaptive
+GEO_HAS_DISK_ADAPTIVE_BATCH = 1  # geo_render_disk_adaptive_batch
 GEO_DISK_PROFILE_POWER = 0
 GEO_DISK_PROFILE_THIN = 1
 GEO_DISK_RAMP_MAX = 1024
@@ -190,6 +191,11 @@ SIGNATURES = {
         _int,
         [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _vp,
          _vp, _vp, _vp, _vp, _vp],
+    ),
+    "geo_render_disk_adaptive_batch": (
+        _int,
+        [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
+         ctypes.c_size_t, _vp, _vp],
     ),
     "geo_steps_flush": (_int, [_vp, _vp, _vp]),
     "geo_set_tile_order": (_int, [_vp, _u32, _u32, _vp]),

@@ -467,6 +467,33 @@ class Context:
             _ptr(out_rgba), _ptr(out_mask), _ptr(out_uv), _ptr(out_steps), _ptr(steps_total),
             _stream_handle(stream)))
 
+    def render_disk_adaptive_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int,
+                                   row_stride: int, nbands: int, out_rgba, frame_stride: int | None = None,
+                                   steps_total=None, stream=None) -> None:
+        """geo_render_disk_adaptive_batch: len(frames) (1 .. GEO_MAX_BATCH_FRAMES) GEO_MODE_ADAPTIVE |
+        GEO_FLAG_DISK frames of the context's disk in one render launch, unshaded, shaded by set_disk_shift or
+        with set_disk_emission, with GEO_FLAG_SS4 on every scene or on none (sizes, rows and bands are then in
+        output pixels); frame f's packed bands at byte f*frame_stride of out_rgba (default: packed back to
+        back).  scenes: one GeoScene for every frame, or one per frame (a moving observer: they may differ in
+        r_obs only).  A one-sample frame is render_disk_adaptive's bit for bit.  Colour only."""
+        n = len(frames)
+        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
+            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
+        scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
+        if len(scenes) != n:
+            raise ValueError("one scene, or one scene per frame")
+        fbytes = nbands * band_rows * width * 4
+        frame_stride = fbytes if frame_stride is None else frame_stride
+        import torch
+
+        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
+        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
+        arr = (GeoFrame * n)(*frames)
+        sarr = (GeoScene * n)(*scenes)
+        check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
+            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
+            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+
 
 def _check_outputs(nrows: int, width: int, rgba, mask, uv, steps, steps_total) -> None:
     """The kernel writes 4 B of RGBA8, 1 B of mask, 2 f32 of UV and one u32 of

@@ -743,6 +743,9 @@ struct RenderCall {
     // frame, through the adaptive disk kernels); every other entry point
     // refuses the disk in that mode
     bool disk_adaptive = false;
+    // geo_render_disk_adaptive_batch (the same scenes, with GEO_FLAG_SS4 or
+    // without, any nframes, through the batched adaptive disk kernels)
+    bool adaptive_batch = false;
     uint32_t width, height, row0, nrows, band_rows, band_stride;
     uint8_t* out_rgba8;
     uint8_t* out_mask = nullptr;  // (a batch draws colour only)
@@ -785,16 +788,22 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     if (rc.disk_adaptive &&
         (scene->mode != GEO_MODE_ADAPTIVE || (scene->flags & ~GEO_FLAG_DEFER_STEPS) != GEO_FLAG_DISK))
         return GEO_EINVAL;
+    // geo_render_disk_adaptive_batch likewise, with SS4 beside them
+    if (rc.adaptive_batch && (scene->mode != GEO_MODE_ADAPTIVE ||
+                              (scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != GEO_FLAG_DISK))
+        return GEO_EINVAL;
     // GEO_FLAG_SS4 (every rule here, where the bit was refused as an unknown
     // one before: a call that breaks an older rule too keeps its status): the
     // one-frame entry points (the ones that draw a disk frame alone) and
     // geo_render_ss_batch, direct mode, the level-0 sampler, colour only (an
     // armed hit or g buffer, consumed by render_impl, refuses the call), DISK
     // and DEFER_STEPS at most, and a sample frame of twice the size that the
-    // entry points take
+    // entry points take.  In the adaptive mode geo_render_disk_adaptive_batch
+    // alone takes the flag, by the same rules.
     w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
-    if (w.ss && (!rc.allow_disk || rc.disk_batch || (!rc.ss_batch && !rc.emit_batch && !rc.ring_batch && rc.nframes != 1) ||
-                 scene->mode != GEO_MODE_DIRECT ||
+    if (w.ss && (!rc.allow_disk || rc.disk_batch ||
+                 (!rc.ss_batch && !rc.emit_batch && !rc.ring_batch && !rc.adaptive_batch && rc.nframes != 1) ||
+                 scene->mode != (rc.adaptive_batch ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
                  (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
                  rc.out_uv || rc.out_steps || w.out_hits || w.out_g || w.out_q || rc.width > (1u << 19) ||
                  rc.height > (1u << 19)))
@@ -804,7 +813,8 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // GEO_FLAG_DISK: the one-frame entry points, geo_render_disk_batch and (with SS4) geo_render_ss_batch, direct
     // mode, DEFER_STEPS at most
     w.disk = (scene->flags & GEO_FLAG_DISK) != 0;
-    if (w.disk && (!rc.allow_disk || scene->mode != (rc.disk_adaptive ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
+    if (w.disk && (!rc.allow_disk ||
+                   scene->mode != (rc.disk_adaptive || rc.adaptive_batch ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
                    (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0))
         return GEO_EINVAL;
     // geo_render_disk_batch draws disk scenes only, and colour only: an armed
@@ -817,6 +827,8 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // geo_render_disk_ring_batch likewise; with the state off it has nothing
     // to draw (GEO_ESTATE, after the disk's below)
     if (rc.ring_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
+    // geo_render_disk_adaptive_batch likewise (its scenes are disk scenes by the rule above)
+    if (rc.adaptive_batch && (w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
     // geo_set_disk_emission: the one-frame entry points and geo_render_emission_batch
     // (through the older batched calls a disk frame would come out without
     // its emission: refused, nothing launched)
@@ -825,8 +837,10 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // geo_set_disk_ring_f64: the one-frame entry points' per-pixel renders
     // and geo_render_disk_ring_batch only (through any other call a
     // supersampled or batched disk frame would come out without its band:
-    // refused, nothing launched)
-    if (w.disk && c->disk_ring && !rc.ring_batch && (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch))
+    // refused, nothing launched; geo_render_disk_adaptive_batch has its rule
+    // below, with geo_render_disk_adaptive's: the state is ignored for rs = 0)
+    if (w.disk && c->disk_ring && !rc.ring_batch && !rc.adaptive_batch &&
+        (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch))
         return GEO_EINVAL;
     // (no capture orbit, rs = 0: the state is ignored, the plain disk frame)
     w.disk_ring = w.disk && c->disk_ring && scene->rs > 0.0f && scene->r_obs > scene->rs;
@@ -864,7 +878,9 @@ static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
             return GEO_EINVAL;
         // geo_render_disk_adaptive with geo_set_disk_ring_f64 on and a capture
         // orbit to draw: the frame would come out without its band
-        if (rc.disk_adaptive && w.disk_ring) return GEO_EINVAL;
+        // (geo_render_disk_adaptive_batch too: its frames share rs, and each
+        // observer is outside the horizon by fill_frames' rule)
+        if ((rc.disk_adaptive || rc.adaptive_batch) && w.disk_ring) return GEO_EINVAL;
     }
     return GEO_OK;
 }
@@ -1333,8 +1349,42 @@ static int launch_ring_frames(geo_ctx* c, const RenderCall& rc, const RenderWork
     });
 }
 
+// Stage 5, geo_render_disk_adaptive_batch: launch_emit_frames' and
+// launch_ring_frames' form with the adaptive disk kernels.  The frames'
+// constants are fill_disk_batch's, the one-frame adaptive launch's own
+// (launch_disk_frame: geo::disk_ray_adaptive reads the same geo::DiskConsts);
+// with GEO_FLAG_SS4, w.fk holds each frame's camera at 2W x 2H and the grid is
+// the sample frame's.
+static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(DiskEmitBatchArgs) + sizeof(SsBatchOut) <= 4096,
+              "kernel arguments fit 4 KiB");
+static int launch_adaptive_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    DiskBatchArgs db;
+    DiskEmitBatchArgs eb;
+    if (const int st = fill_disk_batch(c, rc, w, db, w.emit ? &eb : nullptr)) return st;
+    SsBatchOut x;
+    x.out_width = rc.width;
+    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        if (w.emit) {
+            if (w.ss)
+                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_emit_batch_kernel<KIND>, db, eb,
+                                          x);
+            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_emit_batch_kernel<KIND>, db, eb);
+        }
+        if (c->shift_set) {
+            if (w.ss)
+                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_batch_kernel<KIND, true>, db, x);
+            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_batch_kernel<KIND, true>, db);
+        }
+        if (w.ss)
+            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_batch_kernel<KIND, false>, db, x);
+        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_batch_kernel<KIND, false>, db);
+    });
+}
+
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+    if (rc.adaptive_batch) return launch_adaptive_frames(c, rc, w);
     if (rc.ring_batch) {
         // (no capture orbit, rs = 0: the state is ignored, the older batches' kernels)
         if (w.disk_ring) return launch_ring_frames(c, rc, w);
@@ -1727,6 +1777,23 @@ int geo_render_disk_adaptive(geo_ctx* c, const geo_frame* frame, const geo_scene
     rc.out_mask = out_mask;
     rc.out_uv = out_uv;
     rc.out_steps = out_steps;
+    return render_impl(c, rc);
+}
+
+int geo_render_disk_adaptive_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                                   uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
+                                   uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                                   unsigned long long* steps_total, void* stream) {
+    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
+        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
+        return invalid_call(c);
+    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
+                                out_rgba8, steps_total, stream);
+    rc.nframes = nframes;
+    rc.out_frame_stride = out_frame_stride;
+    rc.scene_per_frame = true;
+    rc.allow_disk = true;
+    rc.adaptive_batch = true;
     return render_impl(c, rc);
 }
 

@@ -655,7 +655,8 @@ __global__ __launch_bounds__(kBlock) void geo_render_kernel(const RenderArgs a, 
 // ---- GEO_FLAG_DISK: the thin accretion disk (geo_disk.h) ----------------
 // The disk renders are kernels of their own beside geo_render_kernel, whose
 // instantiations carry no disk branch, argument or register: GEO_MODE_DIRECT
-// (GEO_MODE_ADAPTIVE in the kernels of geo_render_disk_adaptive),
+// (GEO_MODE_ADAPTIVE in the kernels of geo_render_disk_adaptive and
+// geo_render_disk_adaptive_batch),
 // level-0 sampler, one wave per workgroup on the 1-D grid of the plain
 // direct-mode render (wave_blocks), the same tile mapping, step counting and
 // tile-cost recording.  The argument structs come first, then the ring
@@ -989,9 +990,13 @@ struct DiskEmitBatchArgs {
 //          (mask, uv, steps, hits, g, q; the sky UV also where only a.out_uv
 //          asks for it); every other render is colour only
 //   MODE   the integrator: GEO_MODE_DIRECT (geo::geodesic_angle_disk), or
-//          GEO_MODE_ADAPTIVE (geo::geodesic_angle_adaptive_disk, the one-frame
-//          one-sample disk renders of geo_render_disk_adaptive; a tile's cost
-//          is then in attempts)
+//          GEO_MODE_ADAPTIVE (geo::geodesic_angle_adaptive_disk: the one-frame
+//          one-sample disk renders of geo_render_disk_adaptive with their side
+//          outputs, and the colour-only frames of
+//          geo_render_disk_adaptive_batch on DiskBatchFrame, one sample or SS4;
+//          a tile's cost is then in attempts).  The adaptive loop's lanes
+//          leave it one by one; they rejoin at the end of the in_frame arm, as
+//          the direct loop's do, before the SS4 resolve reads across lanes
 //   SRC    the frame source: what frame z of the launch reads its camera,
 //          scene, disk, texture, shift or emission constants and ramp from,
 //          where its output starts and whether it records tile costs, one
@@ -1010,6 +1015,7 @@ struct SkyFrame {
     const RenderArgs& a;
     const FrameBatch<NF>& fb;
     uint32_t z;  // the frame of the launch (0 of one)
+    static constexpr bool kOneFrame = NF == 1;
     __device__ __forceinline__ const FrameK& f() const { return fb.f[NF > 1 ? z : 0u]; }
     __device__ __forceinline__ const geo::CameraConsts& cam() const { return f().cam; }
     __device__ __forceinline__ const float* movement_to_central() const { return f().frame.movement_to_central; }
@@ -1044,6 +1050,7 @@ struct DiskBatchFrame {
     const DiskBatchArgs& db;
     const E& eb;
     uint32_t z;
+    static constexpr bool kOneFrame = false;
     __device__ __forceinline__ const DiskFrameK& f() const { return db.f[z]; }
     __device__ __forceinline__ const geo::CameraConsts& cam() const { return f().cam; }
     __device__ __forceinline__ const float* movement_to_central() const { return f().movement_to_central; }
@@ -1101,8 +1108,9 @@ struct DiskBatchFrame {
 template <int KIND, Shade SHADE, bool SS, bool SIDE, int MODE = GEO_MODE_DIRECT, typename SRC>
 __device__ __forceinline__ void wave_block_body(const RenderArgs& a, const SRC& src, uint32_t out_width) {
     static_assert(!(SS && SIDE) && !(SIDE && SHADE == Shade::kSky), "side outputs: the one-sample disk renders'");
-    static_assert(MODE == GEO_MODE_DIRECT || (MODE == GEO_MODE_ADAPTIVE && SHADE != Shade::kSky && !SS && SIDE),
-                  "the adaptive integrator: the one-frame one-sample disk renders'");
+    static_assert(MODE == GEO_MODE_DIRECT ||
+                      (MODE == GEO_MODE_ADAPTIVE && SHADE != Shade::kSky && (SIDE ? !SS : !SRC::kOneFrame)),
+                  "the adaptive integrator: the one-frame one-sample disk renders', and the disk batch's frames'");
     // geo_render_kernel's WB mapping: workgroup L draws wave `wave` of the tile
     // at dispatch position pos.  The padding of the last group (a whole
     // workgroup) leaves here: the body's only early exit, and a wave-uniform
@@ -1337,6 +1345,40 @@ __global__ __launch_bounds__(64) void geo_render_ss_emit_batch_kernel(const Rend
                                                                       const SsBatchOut x) {
     wave_block_body<KIND, Shade::kDiskEmit, true, false>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z},
                                                          x.out_width);
+}
+
+// geo_render_disk_adaptive_batch: the disk batch's, the SS batch's disk frames'
+// and the emission batch's kernels with the adaptive integrator (the argument
+// layouts are theirs).
+template <int KIND, bool SHIFT>
+__global__ __launch_bounds__(64) void geo_render_disk_adaptive_batch_kernel(const RenderArgs a,
+                                                                            const DiskBatchArgs db) {
+    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, false, false, GEO_MODE_ADAPTIVE>(
+        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, 0u);
+}
+
+template <int KIND, bool SHIFT>
+__global__ __launch_bounds__(64) void geo_render_ss_adaptive_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                          const SsBatchOut x) {
+    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, true, false, GEO_MODE_ADAPTIVE>(
+        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, x.out_width);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_disk_adaptive_emit_batch_kernel(const RenderArgs a,
+                                                                                 const DiskBatchArgs db,
+                                                                                 const DiskEmitBatchArgs eb) {
+    wave_block_body<KIND, Shade::kDiskEmit, false, false, GEO_MODE_ADAPTIVE>(
+        a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z}, 0u);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void geo_render_ss_adaptive_emit_batch_kernel(const RenderArgs a,
+                                                                               const DiskBatchArgs db,
+                                                                               const DiskEmitBatchArgs eb,
+                                                                               const SsBatchOut x) {
+    wave_block_body<KIND, Shade::kDiskEmit, true, false, GEO_MODE_ADAPTIVE>(
+        a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z}, x.out_width);
 }
 
 // ---- the one body of the batched disk kernels with the f64 band -----------

@@ -238,7 +238,13 @@ class ShardedFrame:
         with set_disk_ring_f64 on goes to geo_render_disk_ring_batch (with
         GEO_FLAG_SS4 or without, with the emission set or not: emission_batch
         is then not needed); without it such a scene is refused, as every
-        other batched entry point refuses it."""
+        other batched entry point refuses it.
+        A GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene needs no keyword: every
+        older call refuses it, so it is routed by what it shows, to
+        geo_render_disk_adaptive_batch with batch_launch (with GEO_FLAG_SS4 or
+        without, any shading) and to geo_render_disk_adaptive without (a
+        supersampled one through the batched call with one frame); while
+        set_disk_ring_f64 is on and rs > 0 it is refused (ValueError)."""
         import torch
 
         from ._lib import lib
@@ -261,7 +267,8 @@ class ShardedFrame:
         self.disk_ring_batch = bool(disk_ring_batch)
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
-        if self.batch:
+        self._refuse_adaptive_ring(scene)
+        if self.batch and not self._adaptive_disk_scene(scene):
             self._refuse_ring_batch(scene)
             self._refuse_emission_batch(scene)
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
@@ -333,6 +340,12 @@ class ShardedFrame:
         L = self.layout
         if L.nbands() == 0:  # a frame too small to give this rank a band
             return
+        sc = self.scene if scene is None else scene
+        if self._adaptive_disk_scene(sc):
+            self._refuse_adaptive_ring(sc)
+            self.ctx.render_disk_adaptive(self.frame if frame is None else frame, sc, self.width, self.height,
+                                          L.band_height(), L.row0(), L.cycle_rows, L.nbands(), buf, **outs)
+            return
         self.ctx.render_band_set(self.frame if frame is None else frame, self.scene if scene is None else scene,
                                  self.width, self.height, L.band_height(), L.row0(), L.cycle_rows, L.nbands(), buf,
                                  **outs)
@@ -360,6 +373,24 @@ class ShardedFrame:
         from ._lib import GEO_FLAG_DISK
 
         return bool(scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_ring_f64", False))
+
+    @staticmethod
+    def _adaptive_disk_scene(scene) -> bool:
+        """A GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene: geo_render_disk_adaptive's
+        and geo_render_disk_adaptive_batch's, which every older call refuses."""
+        from ._lib import GEO_FLAG_DISK, GEO_MODE_ADAPTIVE
+
+        return bool(scene is not None and scene.mode == GEO_MODE_ADAPTIVE and scene.flags & GEO_FLAG_DISK)
+
+    def _refuse_adaptive_ring(self, scene) -> None:
+        """No call draws the adaptive disk's f64 band (geo_set_disk_ring_f64,
+        geo.h): a GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene with a capture orbit
+        (rs > 0) of a context with set_disk_ring_f64 on is refused here, by
+        name, instead of by the launch's GEO_EINVAL."""
+        if self._adaptive_disk_scene(scene) and scene.rs > 0 and getattr(self.ctx, "disk_ring_f64", False):
+            raise ValueError("a GEO_MODE_ADAPTIVE disk scene cannot be drawn with set_disk_ring_f64 on: "
+                             "geo_render_disk_adaptive and geo_render_disk_adaptive_batch draw no f64 band; use "
+                             "set_disk_ring_f64(False), or GEO_MODE_DIRECT")
 
     def _refuse_emission_batch(self, scene) -> None:
         """The older batched entry points draw no emission frames
@@ -392,7 +423,9 @@ class ShardedFrame:
         scenes without it; with emission_batch, geo_render_emission_batch for
         a disk scene while the emission is set; with disk_ring_batch,
         geo_render_disk_ring_batch for a disk scene while set_disk_ring_f64
-        is on), on `stream` (a handle;
+        is on; geo_render_disk_adaptive_batch for a GEO_MODE_ADAPTIVE |
+        GEO_FLAG_DISK scene, with GEO_FLAG_SS4 or without, any shading, no
+        keyword), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
         from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4, GeoFrame, GeoScene, check
@@ -414,9 +447,15 @@ class ShardedFrame:
         # supersampled scenes (with a disk or without) and thin-disk scenes
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
-        self._refuse_ring_batch(scenes[0])
-        self._refuse_emission_batch(scenes[0])
-        if self.disk_ring_batch and self._ring_scene(scenes[0]):
+        adaptive_disk = self._adaptive_disk_scene(scenes[0])
+        if adaptive_disk:  # (every older call refuses it: routed by what the scene shows)
+            self._refuse_adaptive_ring(scenes[0])
+        else:
+            self._refuse_ring_batch(scenes[0])
+            self._refuse_emission_batch(scenes[0])
+        if adaptive_disk:
+            name = "geo_render_disk_adaptive_batch"  # (with GEO_FLAG_SS4 or without, any shading)
+        elif self.disk_ring_batch and self._ring_scene(scenes[0]):
             name = "geo_render_disk_ring_batch"  # (with GEO_FLAG_SS4 or without, any shading)
         elif self.emission_batch and self._emission_scene(scenes[0]):
             name = "geo_render_emission_batch"  # (with GEO_FLAG_SS4 or without)
@@ -547,7 +586,11 @@ class ShardedFrame:
         """Frame i: its bands rendered (batch mode: recorded, and the batch
         rendered in one launch at its K-th frame; `events` time that launch)
         into slot i % K of batch buffer (i // K) % 2.  frame: this frame's
-        uniform (default the one the object was built with)."""
+        uniform (default the one the object was built with).  The per-frame
+        path draws a GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene through
+        geo_render_disk_adaptive, and with GEO_FLAG_SS4 (which has no
+        one-frame call) through geo_render_disk_adaptive_batch with one
+        frame."""
         b, sub = (i // self.K) % 2, i % self.K
         if sub == 0:
             self._retire(b)  # the batch that used this buffer two batches ago
@@ -572,15 +615,31 @@ class ShardedFrame:
 
                 check("geo_time_next_render", st)
         if nb:
-            st = lib.geo_render_band_set(
-                self._ctx_h, self._frame_ref if frame is None else ctypes.byref(frame),
-                self._scene_ref if scene is None else ctypes.byref(scene), self.width,
-                self.height, band_h, row0, cycle, nb, self._lv[b][sub], None, None, None,
-                None if steps_total is None else steps_total.data_ptr(), sh)
+            sc = self.scene if scene is None else scene
+            fref = self._frame_ref if frame is None else ctypes.byref(frame)
+            sref = self._scene_ref if scene is None else ctypes.byref(scene)
+            total = None if steps_total is None else steps_total.data_ptr()
+            if sc.mode == 2 and sc.flags & 16:  # GEO_MODE_ADAPTIVE | GEO_FLAG_DISK (_adaptive_disk_scene)
+                self._refuse_adaptive_ring(sc)
+                if sc.flags & 32:  # GEO_FLAG_SS4
+                    name = "geo_render_disk_adaptive_batch"
+                    st = lib.geo_render_disk_adaptive_batch(
+                        self._ctx_h, fref, sref, 1, self.width, self.height, band_h, row0, cycle, nb,
+                        self._lv[b][sub], self.slice, total, sh)
+                else:
+                    name = "geo_render_disk_adaptive"
+                    st = lib.geo_render_disk_adaptive(
+                        self._ctx_h, fref, sref, self.width, self.height, band_h, row0, cycle, nb, self._lv[b][sub],
+                        None, None, None, total, sh)
+            else:
+                name = "geo_render_band_set"
+                st = lib.geo_render_band_set(
+                    self._ctx_h, fref, sref, self.width, self.height, band_h, row0, cycle, nb, self._lv[b][sub], None,
+                    None, None, total, sh)
             if st != 0:
                 from ._lib import check
 
-                check("geo_render_band_set", st)
+                check(name, st)
         if self.bpp == 3 and self.rank != 0:
             st = lib.geo_pack_rgb(self._ctx_h, self._lv[b][sub], self.slice // 4, self._sv[b][sub], sh)
             if st != 0:

@@ -99,6 +99,19 @@ side's spread ((max - min) / median of its alternation medians) and whether
 the surplus lies beyond twice that spread.  One JSON object.
 
   python tools/bench_disk.py --adaptive [--out profiles/disk_adaptive_bench.json]
+
+--batch K --adaptive measures the batched adaptive disk launch
+(geo_render_disk_adaptive_batch) on --batch's layout with --adaptive's scene,
+by --batch K --ring's method: one launch of K frames alternates with K
+one-frame geo_render_disk_adaptive launches of the same frames back to back
+(the yardstick), unshaded and with --emission's state, each side on its own
+context; --alternations (5) times --n (30) samples of each side per timing
+(stream events around the calls, then the dispatches' own event pairs) after
+--settle (4) alternations kept apart, --sessions (2) sessions.  The batch
+counts as a gain where it is faster than the one-frame side by more than twice
+that side's alternation spread.
+
+  python tools/bench_disk.py --batch 8 --adaptive [--out profiles/disk_adaptive_batch_bench.json]
 """
 from __future__ import annotations
 
@@ -136,10 +149,10 @@ def main():
                         "batch its last (default: the other way round)")
     p.add_argument("--out")
     args = p.parse_args()
-    if args.adaptive and (args.batch or args.ring or args.emission or args.shift):
-        raise SystemExit("--adaptive goes alone")
+    if args.adaptive and (args.ring or args.emission or args.shift):
+        raise SystemExit("--adaptive goes alone, or with --batch K")
     if not args.out:
-        name = "disk_adaptive_bench.json" if args.adaptive else "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
+        name = "disk_adaptive_batch_bench.json" if (args.adaptive and args.batch) else "disk_adaptive_bench.json" if args.adaptive else "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
             args.ring) else "disk_emission_batch_bench_cfg3.json" if (
             args.batch and args.emission) else (
             "disk_batch_bench_cfg3.json") if args.batch else (
@@ -148,6 +161,8 @@ def main():
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
+    if args.adaptive and args.batch:
+        return adaptive_batch_main(args)
     if args.adaptive:
         return adaptive_main(args)
     if args.batch and args.ring:
@@ -957,6 +972,155 @@ def ring_batch_main(args):
                   "of n, after settle alternations of each timing that are kept apart; spread = (max - min) / median of "
                   "a side's alternation medians; margin = 1 - 2 x the one-frame side's spread",
         "sessions": [ring_batch_session(args, cfg, frame, scene, sky, tex) for _ in range(args.sessions)],
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+def adaptive_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission):
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.dist import BandLayout
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent, hipEventDefault
+
+    K = args.batch
+    W, H = cfg.width, cfg.height
+    L = BandLayout(H, 8, 8, 1)  # a peer's share at N = 8
+    band = (L.band_height(), L.row0(), L.cycle_rows, L.nbands())
+    packed = L.packed_rows() * W * 4
+    dev = torch.device("cuda:0")
+    out = torch.empty(K * packed, dtype=torch.uint8, device=dev)
+    sh = torch.cuda.current_stream().cuda_stream
+    frames = (_lib.GeoFrame * K)(*([frame] * K))
+    scenes = (_lib.GeoScene * K)(*([scene] * K))
+    lib = _lib.lib
+
+    def make_ctx(emit):
+        c = g.Context(0)
+        c.set_sky(sky)
+        c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+        if emit:
+            c.set_disk_emission(ramp, **emission)
+        return c
+
+    def run_batch(c, pairs=None):
+        if pairs is not None:
+            c.time_next_render(*pairs[0])
+        _lib.check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
+            c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
+
+    def run_singles(c, pairs=None):
+        for k in range(K):
+            if pairs is not None:
+                c.time_next_render(*pairs[k])
+            _lib.check("geo_render_disk_adaptive", lib.geo_render_disk_adaptive(
+                c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None,
+                None, None, sh))
+
+    # (each side on its own context: the learned dispatch order is kept per context)
+    sides = [("plain_batch", make_ctx(False), run_batch, 1), ("plain_single", make_ctx(False), run_singles, K),
+             ("emission_batch", make_ctx(True), run_batch, 1), ("emission_single", make_ctx(True), run_singles, K)]
+    for _ in range(args.warmup):
+        for _, c, run, _ in sides:
+            run(c)
+    torch.cuda.synchronize()
+    res = {"layout": {"world": 8, "rank": 1, "band_rows": band[0], "row0": band[1], "row_stride": band[2],
+                      "nbands": band[3], "rows": L.rows_mine()}}
+    for how in ("stream_events", "dispatch_events"):
+        med = {name: [] for name, *_ in sides}
+        settling = {name: [] for name, *_ in sides}
+        for alt in range(args.settle + args.alternations):
+            ev = {name: [] for name, *_ in sides}
+            for _ in range(args.n):
+                for name, c, run, m in sides:
+                    if how == "stream_events":
+                        a, b = HipEvent(hipEventDefault), HipEvent(hipEventDefault)
+                        a.record(sh)
+                        run(c)
+                        b.record(sh)
+                        ev[name].append([(a, b)])
+                    else:
+                        pairs = [(HipEvent(), HipEvent()) for _ in range(m)]
+                        run(c, pairs)
+                        ev[name].append(pairs)
+                torch.cuda.synchronize()  # the next sample's launches queue behind nothing
+            for name, v in ev.items():
+                (settling if alt < args.settle else med)[name].append(
+                    float(np.median([sum(a.elapsed_time(b) for a, b in pairs) for pairs in v]) / K))
+        res[how] = {"settling_alternations_not_counted": settling}
+        for tag in ("plain", "emission"):
+            bm, sm = med[tag + "_batch"], med[tag + "_single"]
+            b_m, s_m = float(np.median(bm)), float(np.median(sm))
+            spread = (max(sm) - min(sm)) / s_m
+            res[how][tag] = {
+                "batch_ms_per_frame_medians": bm, "single_ms_per_frame_medians": sm,
+                "batch_ms_per_frame": b_m, "single_ms_per_frame": s_m,
+                "batch_over_single": b_m / s_m, "single_spread": spread, "batch_spread": (max(bm) - min(bm)) / b_m,
+                # the batch is held to a saving of more than twice the one-frame side's own spread
+                "margin": 1.0 - 2.0 * spread, "faster_by_more_than_margin": bool(b_m < s_m * (1.0 - 2.0 * spread)),
+            }
+    # what the frames draw (untimed): the attempts of one batch and of its K one-frame renders
+    tot_b = torch.zeros(1, dtype=torch.int64, device=dev)
+    tot_s = torch.zeros(1, dtype=torch.int64, device=dev)
+    c = sides[0][1]
+    _lib.check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
+        c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, tot_b.data_ptr(), sh))
+    for k in range(K):
+        _lib.check("geo_render_disk_adaptive", lib.geo_render_disk_adaptive(
+            c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None, None,
+            tot_s.data_ptr(), sh))
+    torch.cuda.synchronize()
+    res["attempts_total_batch"], res["attempts_total_singles"] = int(tot_b.item()), int(tot_s.item())
+    for _, c, *_ in sides:
+        c.close()
+    return res
+
+
+def adaptive_batch_main(args):
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, blackbody_ramp, make_disk_texture, make_sky
+
+    K = args.batch
+    if not 1 <= K <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise SystemExit(f"--batch: 1 .. {_lib.GEO_MAX_BATCH_FRAMES}")
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg, cfg5 = CONFIGS["cfg3_4k"], CONFIGS["cfg5_8k_adaptive"]
+    obs = g.Observer(cfg.rs, cfg.fov, cfg.width, cfg.height)
+    obs.set_position(*cfg.position)
+    obs.set_camera(*cfg.camera)
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    scene = g.make_scene(cfg.rs, cfg.sphere_r, obs.get_radial_position(), cfg5.step, cfg5.max_steps,
+                         _lib.GEO_MODE_ADAPTIVE, _lib.GEO_FLAG_DISK, cfg5.tol)
+    emission = dict(t_ref=9000.0, t_lo=1500.0, t_hi=30000.0, profile=_lib.GEO_DISK_PROFILE_THIN, exposure=1.0, spin=1)
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    ramp = blackbody_ramp(256, emission["t_lo"], emission["t_hi"])
+    res = {
+        "config": "cfg3_4k's scene at cfg5_8k_adaptive's mode, step and tol", "width": cfg.width, "height": cfg.height,
+        "step": cfg5.step, "tol": cfg5.tol, "max_steps": cfg5.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs],
+        "emission": emission, "ramp_entries": 256,
+        "frames_per_batch": K, "n": args.n, "alternations": args.alternations, "settle": args.settle,
+        "order_in_a_sample": ["plain_batch", "plain_single", "emission_batch", "emission_single"],
+        "warmup": args.warmup,
+        "timing": "stream_events: a pair of events on the stream around one geo_render_disk_adaptive_batch call of K "
+                  "frames, or around K one-frame geo_render_disk_adaptive launches back to back; dispatch_events: "
+                  "geo_time_next_render pairs on the render dispatches alone, the K one-frame times added; the four "
+                  "sides (unshaded and emission, batch and one-frame) alternate, each on its own context; per "
+                  "alternation the median of n, after settle alternations of each timing that are kept apart; spread = "
+                  "(max - min) / median of a side's alternation medians; margin = 1 - 2 x the one-frame side's spread",
+        "sessions": [adaptive_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission)
+                     for _ in range(args.sessions)],
     }
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

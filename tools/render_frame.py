@@ -9,7 +9,7 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
         [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
-        [--disk-ring-f64] [--adaptive [--tol T]]
+        [--disk-ring-f64] [--adaptive [--tol T] [--ss]]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -30,7 +30,11 @@ accuracy bar), on the GPU or with --cpu, not with --ss.
 --adaptive draws the disk frame with the error-controlled integrator
 (GEO_MODE_ADAPTIVE through geo_render_disk_adaptive, --tol its tolerance in u,
 0 = the default 1e-6), unshaded, with --disk-shift or with --disk-emission, on
-the GPU or with --cpu; not with --ss or --disk-ring-f64.
+the GPU or with --cpu; not with --disk-ring-f64.  With --ss the GPU frame goes
+through geo_render_disk_adaptive_batch with one frame (the only call that
+supersamples an adaptive disk frame), and --cpu renders
+geo_render_cpu_disk_adaptive at twice the size and box-resolves it here
+(GEO_FLAG_SS4's definition: the CPU function refuses the flag).
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -74,6 +78,11 @@ def disk_frame(args):
     sky = imageio.load_texture(args.sky) if args.sky else make_sky("equirect", (2048, 1024))
     tex = make_disk_texture((1024, 128))
     r_in, r_out = args.disk
+    cpu_resolve = args.cpu and args.adaptive and args.ss
+    if cpu_resolve:  # the one-sample frame at 2w x 2h, resolved below
+        scene = g.make_scene(1.0, 50.0, obs.get_radial_position(), math.pi / 100, 2048, _lib.GEO_MODE_ADAPTIVE,
+                             _lib.GEO_FLAG_DISK, args.tol)
+        w, h = 2 * w, 2 * h
     if args.cpu:
         lib = ctypes.CDLL(os.path.join(ROOT, "schwarzschild_raytracer_wgpu_amd", "libgeo_cpu.so"))
         disk = _lib.GeoDisk(r_in, r_out, (ctypes.c_float * 3)(*args.disk_normal), (ctypes.c_float * 3)(1.0, 0.0, 0.0))
@@ -113,6 +122,10 @@ def disk_frame(args):
             rc = lib.geo_render_cpu_disk_shift_ring_f64(*common, ctypes.addressof(shift) if shift else None, None, ring)
         if rc != 0:
             raise SystemExit(f"{name}: {rc}")
+        if cpu_resolve:  # per channel (s00 + s01 + s10 + s11 + 2) >> 2
+            s4 = rgba.astype(np.uint16)
+            rgba = ((s4[0::2, 0::2] + s4[0::2, 1::2] + s4[1::2, 0::2] + s4[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+            w, h = w // 2, h // 2
     else:
         import torch
 
@@ -127,7 +140,12 @@ def disk_frame(args):
         if args.disk_ring_f64:
             ctx.set_disk_ring_f64(True)
         rgba = torch.empty(w * h * 4, dtype=torch.uint8, device="cuda:0")
-        if args.adaptive:
+        if args.adaptive and args.ss:  # (a whole frame of 8-row bands, the last one clipped)
+            nb = (h + 7) // 8
+            rgba = torch.empty(nb * 8 * w * 4, dtype=torch.uint8, device="cuda:0")
+            ctx.render_disk_adaptive_batch([frame], scene, w, h, 8, 0, 8, nb, rgba)
+            rgba = rgba[:w * h * 4]
+        elif args.adaptive:
             ctx.render_disk_adaptive(frame, scene, w, h, h, 0, h, 1, rgba)
         else:
             ctx.render_rows(frame, scene, w, h, 0, h, rgba)
@@ -171,8 +189,8 @@ def main():
     p.add_argument("--disk-ring-f64", action="store_true",
                    help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); not with --ss")
     p.add_argument("--adaptive", action="store_true",
-                   help="with --disk: the error-controlled integrator (geo_render_disk_adaptive); not with --ss or "
-                        "--disk-ring-f64")
+                   help="with --disk: the error-controlled integrator (geo_render_disk_adaptive; with --ss "
+                        "geo_render_disk_adaptive_batch with one frame); not with --disk-ring-f64")
     p.add_argument("--tol", type=float, default=0.0, help="with --adaptive: the tolerance in u (0 = 1e-6)")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
@@ -182,8 +200,8 @@ def main():
     args = p.parse_args()
     if args.disk_ring_f64 and (not args.disk or args.ss):
         p.error("--disk-ring-f64 goes with --disk and without --ss (a supersampled disk frame refuses the state)")
-    if args.adaptive and (not args.disk or args.ss or args.disk_ring_f64):
-        p.error("--adaptive goes with --disk and without --ss and --disk-ring-f64 (the adaptive disk has neither)")
+    if args.adaptive and (not args.disk or args.disk_ring_f64):
+        p.error("--adaptive goes with --disk and without --disk-ring-f64 (the adaptive disk has no f64 band)")
     if args.tol != 0.0 and not args.adaptive:
         p.error("--tol goes with --adaptive")
     if args.disk:
