@@ -147,7 +147,14 @@ typedef enum geo_status {
                                    image over the shadow, the third one at the photon ring);
                                    crossing k is a hit when the main loop integrated that far
                                    (before its exit by crossing, escape, horizon or budget)
-                                   and r_in <= r <= r_out there.  The hits' level-0 samples
+                                   and r_in <= r <= r_out there.  "That far" is decided on
+                                   what the loop returns: the crossing's node floor(a_k / step)
+                                   lies below the step count and a_k below the returned
+                                   traveled angle (NO_VALUE = 15 for a ray that never crosses
+                                   the sphere).  For a step above about 2.2 the reference's
+                                   three Newton iterations need not converge, and the returned
+                                   angle can lie before a crossing the loop has passed: such
+                                   a crossing is no hit.  The hits' level-0 samples
                                    of the disk texture are blended far to near (k = 2, 1, 0)
                                    with the reference's 8-bit alpha blend over what the plain
                                    render writes; mask, UV, steps and steps_total are the

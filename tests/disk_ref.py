@@ -14,7 +14,38 @@ numpy, f64, no code shared with csrc/geo_disk.h:
   sphere, u <= 1/sphere_r; before the horizon, u > 1/rs with u' > 0; before
   the budget max_steps * step) and r_in <= 1/u(a_k) <= r_out.
 
-It holds for every observer between the horizon and the sky sphere (or
+At step/8 (sub=8, the truth of the pi/100 layers) "within the angle the loop
+integrates" is left to u(a_k) itself: a ray that left the sphere inside the fine
+step before a_k shows u(a_k) < 1/sphere_r, outside the annulus.  That holds in
+the continuum and at a fine step.  At the scene's own step (sub=1, the same
+discrete map in f64: it measures the rounding of the path, not truncation, and
+so is an answer at every step and budget) it does not, and trace states the
+rule's remaining clauses as geo.h has them, in f64 and from the reference's own
+text (sphere_ray_tracer.rs:60-191 restated: _ended_before_the_loop, the loop's
+exit tests with `bound`, _newton):
+
+* crossing k counts only while its node floor(a_k / step) lies below the step
+  count (the loop executed the step that starts there);
+* crossing k counts only while a_k lies below the traveled angle the loop
+  returns: node * step + Newton's step length (three iterations from the steeper
+  end) where the stopping step crosses the sphere, NO_VALUE = 15 > a_2 otherwise;
+* a ray that the reference's pre-filters or radial cases end before the loop
+  draws nothing.
+
+The second clause is not implied by u(a_k): for step > 2.28 three Newton
+iterations on an RK4 step of that length do not converge and can return a
+negative length (-0.2 step to -1271 steps where it matters), so the returned
+angle lies below a crossing the loop has already probed with u(a_k) inside the
+annulus.  On tests/fuzz_disk_scenes.py's seeds 0..399 that happens on 244 slots
+of six seeds (tests/disk_step_truth.py's ANGLE_CLAUSE_SEEDS), every one of them
+"u(a_k) in the annulus, a_k >= angle"; with the clause stated the CPU path and
+this trace disagree on no slot off the annulus' edges, and the pre-filters and
+the node clause change none (the observers inside the photon sphere included).
+The constants below, TOL_R_BAND and disk_truth.py's were all measured with sub=8
+or at step pi/100, where Newton's length lies inside its step: none of them moves
+(tests/test_disk_step_truth_cpu.py::test_the_clauses_change_nothing_at_the_truth_step).
+
+The sub=8 trace holds for every observer between the horizon and the sky sphere (or
 rs = 0) as long as the disk lies outside the photon sphere, r_in > 1.5 rs,
 which GEO_FLAG_DISK's scenes in tests/fuzz_disk_scenes.py keep.  Inside the
 photon sphere the reference's pre-filters (sphere_ray_tracer.rs:106-119) end
@@ -60,6 +91,8 @@ TOL_R = 2.0 ** -13   # 1.22e-4: 4 * CAL_R = 1.0e-4 rounded up to a power of two
 TOL_AZ = 2.0 ** -20  # 9.5e-7: 4 * CAL_AZ = 6.0e-7 rounded up to a power of two
 BAND_X = 0.02     # |b/b_c - 1| below which a pixel is left to the bit-equality tests
 MAX_CROSSINGS = 3
+NO_VALUE = 15.0   # the traveled angle of a ray that never crosses the sky sphere (sphere_ray_tracer.rs:22)
+NEWTON_STEP_MAX = 0.5  # the step up to which Newton's length lies inside its step (trace, sub=1)
 
 CAL_DISKS = [((9.0, 2.0, 4.0), 3.0, 9.0, (0.2, 0.1, 1.0)), ((3.1, 0.4, 0.9), 1.6, 2.2, (0.2, 0.1, 1.0))]
 CAL_CAMS = [(0.0, 0.0), (0.25, 0.1), (-0.3, 0.05), (0.1, -0.2), (-0.15, 0.15)]
@@ -124,23 +157,63 @@ def _rk4(u, v, h, c):
     return u + h / 6.0 * (k1u + 2 * k2u + 2 * k3u + k4u), v + h / 6.0 * (k1v + 2 * k2v + 2 * k3v + k4v)
 
 
+def _ended_before_the_loop(rs, R, r0, E, st, ct):
+    """The rays the reference's radial cases and pre-filters end before the RK4 loop
+    (sphere_ray_tracer.rs:60-119, restated for r0 > rs): they integrate nothing and draw
+    no disk.  st, ct: sin and cos of the ray's angle to the black hole."""
+    rotation = r0 * ct
+    falling = st > 0.0
+    inside_sphere, sphere_outside = r0 < R, R > rs
+    with np.errstate(divide="ignore"):
+        inv_b2 = (E / rotation) ** 2
+    barrier = (rs > 0.0) & (inv_b2 < 4.0 / (27.0 * rs * rs)) if rs > 0.0 else np.zeros(st.shape, dtype=bool)
+    r3_2 = 1.5 * rs
+    different_sides = ((r0 < r3_2) != (R < r3_2)) and abs(r0 - r3_2) > 1e-10
+    return ((rotation < 1e-10) | (inside_sphere and not sphere_outside) | (barrier & different_sides) |
+            ((r0 < r3_2 and inside_sphere) & falling) | ((r0 > r3_2 and not inside_sphere) & ~falling))
+
+
+def _newton(u, v, nu, nv, su, h, c):
+    """The reference's three Newton iterations on the step length from the steeper end
+    (sphere_ray_tracer.rs:150-181): the length at which the RK4 map from (u, v) meets su."""
+    first = np.abs(v) > np.abs(nv)
+    ns = np.where(first, 0.0, h)
+    wu, wv = np.where(first, u, nu), np.where(first, v, nv)
+    for _ in range(3):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ns = ns - (wu - su) / wv
+            wu, wv = _rk4(u, v, ns, c)
+    return ns
+
+
 # wrong traces for tests/disk_truth.py's mutation test: the aberration dropped (k = 0),
 # E = 1 in the initial slope, flat geodesics in a curved scene (c = 0), the azimuth's sense
 # flipped, the slots shifted by one (slot k holds crossing k + 1), and the budget ignored
 # (in the crossing condition and in t_end)
+RULES = ("full", "no_angle_clause", "u_only")
 MUTATIONS = ("no_aberration", "slope_e1", "flat_c", "az_flipped", "slot_shift", "budget_ignored")
 
 
 def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis=(1.0, 0.0, 0.0), sub=8,
-          mutation=None):
+          mutation=None, rule=None):
     """dict: hit (h, w, 3) bool, r, az (h, w, 3) f64 (radius and azimuth in
     turns in [0, 1) of each crossing, nan where the ray never got there), x
     (h, w) = |b/b_c - 1| (inf for rs = 0), theta (h, w), cond (h, w) = hypot(A, B)
-    of a_0 = atan2(-B, A) (the docstring's conditioning of a_0).
+    of a_0 = atan2(-B, A) (the docstring's conditioning of a_0); with sub=1 also
+    angle (h, w), the traveled angle of the sphere crossing (NO_VALUE where the ray
+    never crosses), steps (h, w), the executed steps, and node (h, w, 3) = floor(a_k / step).
+
+    rule: one of RULES; None is "full" with sub=1 (the scene's own step: the hit rule
+    stated in full) and "u_only" otherwise (the three clauses of the module's docstring
+    left to u(a_k), as before they were stated; the only rule off the scene's own step).
+    "no_angle_clause" drops the clause a_k < angle alone: what
+    tests/test_disk_step_truth_cpu.py's named seeds are shown on.
 
     mutation: None, or one of MUTATIONS: a deliberately wrong trace that
     tests/disk_truth.py's checks must refuse (nothing else reads it)."""
     assert mutation is None or mutation in MUTATIONS, mutation
+    rule = ("full" if sub == 1 else "u_only") if rule is None else rule
+    assert rule in RULES and (sub == 1 or rule == "u_only"), (sub, rule)
     rs, R, r0 = float(scene.rs), float(scene.sphere_r), float(scene.r_obs)
     step, budget = float(scene.step), int(scene.max_steps)
     c2 = camera(frame, width, height, k=0.0 if mutation == "no_aberration" else None)
@@ -168,9 +241,20 @@ def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis
         budget = 2 ** 30
     t_end = min(float(ak.max()) + step, budget * step)
     nsub = int(math.ceil(t_end / h))
+    full = rule != "u_only"  # the rule's remaining clauses (the docstring)
     alive = np.ones(rho.shape, dtype=bool)
+    angle = np.full(rho.shape, NO_VALUE)
+    steps = np.full(rho.shape, budget, dtype=np.int64)
+    if full:
+        alive &= ~_ended_before_the_loop(rs, R, r0, E, st, rho / np.hypot(rho, st)) & (budget > 0)
+        steps[~alive] = 0
+        bound = 0.9 * min(1.0 / r0, 1.0 / max(R, 1.5 * rs))
+        if step > NEWTON_STEP_MAX:
+            nsub = int(scene.max_steps)  # (the loop ends with the last ray)
     uk = np.full(ak.shape, np.nan)
     for i in range(nsub):
+        if not alive.any():
+            break
         t0, t1 = i * h, (i + 1) * h
         for k in range(MAX_CROSSINGS):
             m = alive & (ak[..., k] >= t0) & (ak[..., k] < t1) & (ak[..., k] < budget * step)
@@ -181,11 +265,22 @@ def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis
                 uk[..., k][m] = uu
         nu, nv = _rk4(u, v, h, c)
         gone = (nu <= su) | ((nu > hu) & (nv > 0.0)) | ~np.isfinite(nu)
+        if full:
+            # the loop's exit as the reference states it (sphere_ray_tracer.rs:134-191): the step
+            # that crosses the sphere ends the ray at angle + Newton's step length, one that
+            # falls below `bound` or into the horizon ends it with NO_VALUE
+            cross = alive & ((nu > su) != (u > su))
+            gone = cross | (nu < bound) | ((nu > hu) & (nv > 0.0)) | ~np.isfinite(nu)
+            if cross.any():
+                angle[cross] = t0 + _newton(u[cross], v[cross], nu[cross], nv[cross], su, h, c)
+            steps[alive & gone] = i + 1
         u = np.where(alive, nu, u)
         v = np.where(alive, nv, v)
         alive &= ~gone
-        if not alive.any():
-            break
+    if rule == "full":
+        # (a crossing's node lies below the step count exactly where the ray was alive when its
+        # step began, which the loop above already asks; the angle is known only now)
+        uk = np.where(ak < angle[..., None], uk, np.nan)
     with np.errstate(divide="ignore", invalid="ignore"):
         r = 1.0 / uk
     hit = np.isfinite(r) & (r >= r_in) & (r <= r_out)
@@ -197,7 +292,9 @@ def trace(frame, scene, width, height, r_in, r_out, normal=(0.0, 0.0, 1.0), axis
         x = np.abs(r0 * np.cos(theta) / E / (1.5 * math.sqrt(3.0) * rs) - 1.0)
     else:
         x = np.full(theta.shape, np.inf)
-    return dict(hit=hit, r=r, az=az, x=x, theta=theta, cond=np.hypot(A, B))
+    with np.errstate(invalid="ignore"):
+        node = np.floor(ak / step)
+    return dict(hit=hit, r=r, az=az, x=x, theta=theta, cond=np.hypot(A, B), angle=angle, steps=steps, node=node)
 
 
 def az_err(a, b):

@@ -17,9 +17,12 @@ answer, RK4 at step/8, is an answer only where the f32 path's RK4 truncation is
 below the bar), max_steps 2048, every third seed one of SHORT_BUDGETS instead
 (the budget then cuts crossings), in the direct mode or in the adaptive mode
 (tol 0, 1000 attempts: neither the attempts nor disk_ref's angle budget
-1000 step = 10 pi binds).  The seed's own step and budget stay with the
-bit-equality tests (tests/test_host_disk_fuzz.py, test_gpu_disk_fuzz.py) and the
-per-step definition (tests/test_disk_probe_host.py).
+1000 step = 10 pi binds).  The seed's own step and budget (kCurvedIn
+among them) meet the f64 answer in tests/disk_step_truth.py, and the band
+x < 0.005 with the f64 state on in tests/disk_band_truth.py, both against
+disk_ref.trace(sub=1); the bit-equality tests (tests/test_host_disk_fuzz.py,
+test_gpu_disk_fuzz.py) and the per-step definition (tests/test_disk_probe_host.py)
+stay as they are.
 
 Seeds.  Tested: 0..399.  Calibration: 1000..1199, never tested.
 
@@ -228,22 +231,26 @@ def prefetch(seeds, mutations=(None,), workers=None):
     2304 pixels, one Python loop each, and independent.  At most 8 workers; one
     process where this one has a GPU context (a fork would share it) or cannot
     fork.  tests/test_gpu_disk_truth.py does not call it."""
+    keys = [k for k in dict.fromkeys((s, c and budget_of(s) != BUDGET, m) for s in seeds for m in mutations
+                                     for c in ((True, False) if m is None else (True,))) if k not in _TRACES]
+    for key, ref in trace_all(_trace, keys, workers):
+        _keep(key, ref)
+
+
+def trace_all(trace_of, keys, workers=None):
+    """[(key, trace_of(key))]: prefetch's forked workers, with its guard (the other
+    layers' references go through it too)."""
     import multiprocessing
     import os
     import sys
 
-    keys = [k for k in dict.fromkeys((s, c and budget_of(s) != BUDGET, m) for s in seeds for m in mutations
-                                     for c in ((True, False) if m is None else (True,))) if k not in _TRACES]
     workers = min(8, os.cpu_count() or 1, len(keys)) if workers is None else workers
     torch = sys.modules.get("torch")
     if workers > 1 and "fork" in multiprocessing.get_all_start_methods() and \
             not (torch is not None and torch.cuda.is_initialized()):
         with multiprocessing.get_context("fork").Pool(workers) as pool:
-            for key, ref in zip(keys, pool.map(_trace, keys, chunksize=1)):
-                _keep(key, ref)
-    else:
-        for key in keys:
-            _keep(key, _trace(key))
+            return list(zip(keys, pool.map(trace_of, keys, chunksize=1)))
+    return [(key, trace_of(key)) for key in keys]
 
 
 # ---- what is rendered -----------------------------------------------------------
@@ -306,17 +313,24 @@ def thin_amp(r_in, r):
         return np.abs(-0.75 + 0.125 * s / (1.0 - s))
 
 
-def errors(c, what, got, mutation=None):
+def errors(c, what, got, mutation=None, refs=None, spec=None, region=None):
     """The per-slot errors of one render against the seed's reference (mutated or
     not), as flat arrays: what `judge` holds to the bars and `calibrate` takes the
-    maxima of.  The masks (band, H) always come from the unmutated trace."""
-    mode, outputs = WHAT[what]
-    cut = mode == "direct"
-    true = reference(c.seed, cut)
-    ref = reference(c.seed, cut, mutation) if mutation in D.MUTATIONS else true
+    maxima of.  The masks (band, H) always come from the unmutated trace.
+
+    The other layers (tests/disk_band_truth.py, disk_step_truth.py) pass their own
+    refs = (the unmutated trace, the trace compared with), spec = (mode, outputs) for a
+    render WHAT does not name, and region = the (h, w) mask of the pixels they compare
+    in place of x >= BAND_X (and BAND_G); H >= H_MIN is always asked."""
+    mode, outputs = WHAT[what] if spec is None else spec
+    cut = mode != "adaptive"
+    true = reference(c.seed, cut) if refs is None else refs[0]
+    ref = (reference(c.seed, cut, mutation) if mutation in D.MUTATIONS else true) if refs is None else refs[1]
     r_in, r_out, normal, axis = c.disk_args
     x, cond = true["x"], true["cond"]
-    keep = (x >= D.BAND_X) & (cond >= H_MIN)
+    region_g = (x >= S.BAND_G) if region is None else region
+    region = (x >= D.BAND_X) if region is None else region
+    keep = region & (cond >= H_MIN)
     hits = got["hits"]
     e = dict(mode=mode, seed=c.seed)
     rows = {n: [] for n in ("er", "ea", "h", "x", "slot", "dis_edge", "dis_h", "dis_x")}
@@ -324,7 +338,7 @@ def errors(c, what, got, mutation=None):
     for k in range(D.MAX_CROSSINGS):
         g, w = hits[..., k, 0] > 0.0, ref["hit"][..., k]
         both = g & w & keep
-        dropped += int((g & w & (x >= D.BAND_X) & (cond < H_MIN)).sum())
+        dropped += int((g & w & region & (cond < H_MIN)).sum())
         rr = ref["r"][..., k]
         rows["er"].append(np.abs(hits[..., k, 0][both].astype(np.float64) / rr[both] - 1.0))
         rows["ea"].append(D.az_err(hits[..., k, 1][both], ref["az"][..., k][both]))
@@ -340,12 +354,12 @@ def errors(c, what, got, mutation=None):
     e.update({n: np.concatenate(v) for n, v in rows.items()})
     e["dropped"] = dropped
     if "g" in outputs:
-        spin = c.shift[0] if what == "shift" else c.em[0]
+        spin = c.em[0] if "q" in outputs else c.shift[0]
         scene = c.direct if cut else c.adaptive
         gr = S.shift(c.frame, scene, W, H, ref, normal, axis, -spin if mutation == "g_spin" else spin)
         if mutation == "g_no_doppler":
             gr = gr / S.observer_doppler(c.frame, W, H)[..., None]
-        keepg = (x >= S.BAND_G) & (cond >= H_MIN)
+        keepg = region_g & (cond >= H_MIN)
         both = (hits[..., 0] > 0.0) & ref["hit"] & keepg[..., None]
         e["eg"] = np.abs(got["g"][both].astype(np.float64) / gr[both] - 1.0)
         e["g_h"] = np.broadcast_to(cond[..., None], both.shape)[both]
@@ -395,9 +409,9 @@ def bars(e):
 ASSERTIONS = ("hits", "radius", "azimuth", "g", "q")
 
 
-def judge(e):
-    """Per assertion, the number of slots outside the model's bar."""
-    b = bars(e)
+def judge(e, b=None):
+    """Per assertion, the number of slots outside the model's bar (b: another layer's bars)."""
+    b = bars(e) if b is None else b
     out = dict(hits=int((e["dis_edge"] > b["hits"]).sum()), radius=int((e["er"] > b["radius"]).sum()),
                azimuth=int((e["ea"] > b["azimuth"]).sum()), g=0, q=0)
     if "eg" in e:
@@ -412,20 +426,24 @@ def _max(a, w=None):
     return float(a.max()) if a.size else 0.0
 
 
-def check(r, what, seeds):
+def check(r, what, seeds, layer=None):
     """Renders `what` on every seed, holds it to the model and prints the maxima.
     Returns the statistics the reach assertions read; raises on the first
-    assertion of ASSERTIONS that any seed fails."""
-    mode = WHAT[what][0]
+    assertion of ASSERTIONS that any seed fails.  layer: this module, or another
+    layer's (its WHAT, case_of, render, errors and bars)."""
+    import sys
+
+    layer = sys.modules[__name__] if layer is None else layer
+    mode = layer.WHAT[what][0]
     bad, worst = [], {}
-    stats = dict(compared=0, slot1=0, dropped=0, per_seed={}, kinds=set())
+    stats = dict(compared=0, slot1=0, slot2=0, dropped=0, per_seed={}, kinds=set())
     for seed in seeds:
-        c = case_of(seed)
-        e = errors(c, what, render(r, what, c))
-        v = judge(e)
+        c = layer.case_of(seed)
+        e = layer.errors(c, what, layer.render(r, what, c))
+        b = layer.bars(e)
+        v = judge(e, b)
         if any(v.values()):
             bad.append(f"{c.desc}: {what} on {r.name}: outside the bar: {v}")
-        b = bars(e)
         for name, err, bar in (("radius", e["er"], b["radius"]), ("azimuth", e["ea"], b["azimuth"]),
                                ("g", e.get("eg"), b.get("g")), ("q", e.get("eq"), b.get("q"))):
             if err is not None and err.size:
@@ -433,6 +451,7 @@ def check(r, what, seeds):
                 w[0], w[1] = max(w[0], float(err.max())), max(w[1], float((err / bar).max()))
         stats["compared"] += e["er"].size
         stats["slot1"] += int((e["slot"] == 1).sum())
+        stats["slot2"] += int((e["slot"] == 2).sum())
         stats["dropped"] += e["dropped"]
         stats["per_seed"][seed] = e["er"].size
         stats["kinds"].add(c.kind)

@@ -4,7 +4,10 @@ band_lambda_disk with csrc/geo_disk.h): the third image's radii against the
 f64 restatement tests/disk_ref.py at the scene's own step, that nothing
 outside the band changes, that the sky side is the plain GEO_FLAG_RING_F64
 render's, the shaded and emission renders inside the band, and the rules.
-tests/test_gpu_disk_ring.py ties the kernels to this path bit for bit."""
+tests/test_gpu_disk_ring.py ties the kernels to this path bit for bit.
+The flat bar disk_ring_ref.TOL_R_BAND holds on the three poses used here; on
+fuzzed scenes (tests/disk_band_truth.py, test_disk_band_truth_cpu.py) the band's
+radius carries a 1/H term, which that layer's model has."""
 import ctypes
 import math
 import os

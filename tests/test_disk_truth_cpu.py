@@ -93,7 +93,8 @@ def test_against_the_f64_answer(cpu, reach, what):
     assert inside >= 2_000, inside
     # kCurvedOut and kFlat: at step pi/100 no GEO_FLAG_DISK scene is kCurvedIn (geo_pixel.h's
     # make_consts takes it for other steps or an observer inside the horizon, which the flag
-    # refuses); that kind's probes stay with the bit-equality tests on the seeds' own steps
+    # refuses); that kind's probes meet the f64 answer at the seeds' own steps
+    # (tests/disk_step_truth.py, test_disk_step_truth_cpu.py)
     assert s["kinds"] == {0, 2}
 
 

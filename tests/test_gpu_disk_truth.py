@@ -78,5 +78,6 @@ def test_against_the_f64_answer(dev, seeds, what):
         gpu.close()
     assert all(n >= 50 for n in s["per_seed"].values()), s["per_seed"]
     assert s["compared"] >= 50 * len(seeds) and s["slot1"] >= 100
-    # kCurvedOut and kFlat (tests/test_disk_truth_cpu.py says why not kCurvedIn)
+    # kCurvedOut and kFlat (tests/test_disk_truth_cpu.py says why not kCurvedIn;
+    # tests/test_gpu_disk_step_truth.py holds the kCurvedIn disk kernels to the f64 answer)
     assert s["kinds"] == {0, 2}
