@@ -234,6 +234,9 @@ void geo_oracle_pixel_f64(const geo_frame* f, const geo_scene* s, const float* f
 
 static inline float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 static inline float maxz(float a, float b) { return a > b ? a : b; }
+/* geo_math.h min_nan_b_: any NaN a, signaling too, gives b (glibc's fminf
+ * answers a signaling NaN with a NaN; the kernel's v_min_f32 does not) */
+static inline float min_nan_b(float a, float b) { return a < b ? a : b; }
 
 void geo_oracle_sincosf(float x, float* so, float* co) {
     float j = rintf(x * 0.636619772367581343076f);
@@ -258,7 +261,7 @@ void geo_oracle_sincosf(float x, float* so, float* co) {
 }
 
 float geo_oracle_asinf(float x) {
-    float a = fminf(fabsf(x), 1.0f); /* NaN -> 1 (geo_math.h asinf_) */
+    float a = min_nan_b(fabsf(x), 1.0f); /* NaN -> 1 (geo_math.h asinf_) */
     int big = a > 0.5f;
     float z, sq;
     if (big) {
@@ -320,7 +323,7 @@ void geo_oracle_sincos_sky(float x, float* so, float* co) {
 }
 
 float geo_oracle_acos_pi(float x) {
-    float a = fminf(fabsf(x), 1.0f); /* NaN -> 1 */
+    float a = min_nan_b(fabsf(x), 1.0f); /* NaN -> 1 */
     float s = o_sqrt_unit(1.0f - a);
     float p = fmaf(8.312922437e-04f, a, -3.820668207e-03f);
     p = fmaf(p, a, 8.837061934e-03f);

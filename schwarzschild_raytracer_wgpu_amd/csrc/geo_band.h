@@ -170,13 +170,18 @@ GEO_HD bool band_out(const BandConsts& k, double x) { return !(x >= k.lo) | (x >
 
 // IEEE minNum of two doubles (a NaN operand yields the other) as one
 // v_min_f64 (hipcc would canonicalise both operands first; the states are
-// arithmetic results, never signaling NaNs).
+// arithmetic results, never signaling NaNs).  Of +0 and -0 v_min_f64 returns
+// -0 (IEEE 754-2019 minimumNumber); C leaves fmin's choice open and the
+// host's returned its first operand (tests/native/band_consts_device.hip
+// found it; the callers only compare the result, so no frame saw it), so the
+// host picks the negative zero itself.
 GEO_HD double min64_(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 #else
+    if (a == b) return __builtin_signbit(a) ? a : b;
     return __builtin_fmin(a, b);
 #endif
 }

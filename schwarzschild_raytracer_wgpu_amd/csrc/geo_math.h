@@ -14,7 +14,13 @@
 // [-pi/4, pi/4], asin on [0, 1/2], atan on [-(sqrt2-1), sqrt2-1]); the
 // per-pixel sky-direction forms (end of file): reduction by pi, acos/pi as
 // sqrt(1 - |x|) P(|x|), atan2 in turns.  Accuracy is checked against libm in
-// tests/test_math.py (<= 3 ulp / 2e-7 abs on the ranges used).
+// tests/test_math.py (samples of the oracle's mirror), and for every f32 input
+// on the GPU against the device's f64 library, with the device's bits against
+// the host build of this header and the oracle's mirror, by
+// tests/native/transcendentals_exhaustive.hip (tests/test_gpu_transcendentals.py;
+// its host twin tests/test_transcendentals_host.py): asinf_, acosf_ <= 3 ulp,
+// atan2f_ <= 4 ulp, sincosf_ <= 2e-7 abs for |x| < 1e4, the sky forms as stated
+// at each below.
 #pragma once
 
 #if defined(__HIP__)  // HIP language mode (hipcc compiles .cpp as HIP too)
@@ -120,6 +126,21 @@ GEO_HD float divf_(float a, float b) { return a * rcpf_(b); }
 GEO_HD float clampf_(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 // max(a, b) with a NaN `a` mapped to b (used to clamp radicands at 0).
 GEO_HD float fmaxf_(float a, float b) { return a > b ? a : b; }
+// min(a, b) with any NaN `a`, quiet or signaling, mapped to b (the clamp of
+// |x| to 1 in asinf_ and acos_pi_).  On the device one v_min_f32, which
+// answers a signaling NaN like a quiet one.  A host fminf need not: glibc's
+// returns a NaN for a signaling NaN operand, so a g++ build (and the oracle's
+// mirror, which used it) gave NaN where the kernel gives asin(+-1), and
+// acos_pi_ left [0, 1] (tests/native/transcendentals_exhaustive.hip found it;
+// no arithmetic produces a signaling NaN, so no frame saw it).  The host takes
+// the compare and select, equal to the device for every operand.
+GEO_HD float min_nan_b_(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fminf(a, b);
+#else
+    return a < b ? a : b;
+#endif
+}
 
 // sin and cos of x, |x| < ~1e4.
 // rint(t) and (int)rint(t) & 3 for |t| < 2^22 by the 1.5 * 2^23 shifter: t + M
@@ -153,7 +174,7 @@ GEO_HD void sincosf_(float x, float* s, float* c) {
 // kept the NaN: 4 VALU for no case a frame produces), the sign restored by
 // the final copysign.
 GEO_HD float asinf_(float x) {
-    const float a = __builtin_fminf(__builtin_fabsf(x), 1.0f);
+    const float a = min_nan_b_(__builtin_fabsf(x), 1.0f);
     const bool big = a > 0.5f;
     const float z = big ? 0.5f * (1.0f - a) : a * a;
     // the square root only where it is used: a wave with no |x| > 1/2 lane
@@ -208,9 +229,12 @@ GEO_HD float atanf_(float x) { return atan2f_(x, 1.0f); }
 
 // ---- The per-pixel sky-direction transcendentals (round 6) ----
 // Specified for what they feed: angles in turns and half-turns, absolute
-// error <= 2e-7 (tools/fit_sky_polys.py fits the polynomials;
-// tests/test_math.py checks the error), against a UV bar of 1e-4.  The
-// general-purpose forms above stay for the point path and the observer.
+// error <= 2e-7 on the inputs a sampled pixel hands them (sincos_sky_: on
+// [-7, pi/2], see below; acos_pi_ <= 1.5e-7, atan2_turns_ <= 1e-7), against a
+// UV bar of 1e-4.  tools/fit_sky_polys.py fits the polynomials; the error is
+// measured over every input on the GPU (tests/test_gpu_transcendentals.py) and
+// on samples in tests/test_math.py.  The general-purpose forms above stay for
+// the point path and the observer.
 
 // sqrt(max(x, 2^-96)), correctly rounded, for x in [0, 1]: sqrtf_'s fast
 // sequence with the range test replaced by the max (x = 0 gives 2^-48; the
@@ -229,9 +253,35 @@ GEO_HD float sqrt_unit_(float x) {
 
 // sin and cos of x, |x| < 2^21: j = rint(x / pi) by the 1.5 * 2^23 shifter
 // (one fma; its sum's low mantissa bit is j's parity), r = x - j pi in two
-// Cody-Waite parts (|r| <= pi/2 + 1 ulp; pi - P1 - P2 = 5e-12), cubic
-// polynomials in r^2, and both signs flipped for odd j by an XOR of the
-// parity bit.  17 VALU.
+// Cody-Waite parts (pi - P1 - P2 = 5.13e-12), cubic polynomials in r^2, and
+// both signs flipped for odd j by an XOR of the parity bit.  17 VALU.
+//
+// Absolute error, of sin and of cos:
+//  * <= 2e-7 on [-7, fl(pi/2) + 2^-20], every lambda' a sampled pixel of a
+//    converged scene hands it (the mask is lambda' < -7).  This is measured,
+//    over every f32 in the range: 1.82e-7, at x = -+1.5714006 (cos next to
+//    r = +-pi/2, where 1 + z C(z) cancels).
+//  * <= A + B |x| = 2.10e-7 + 2.0e-12 |x| for every |x| < 2^21, derived:
+//      1.50e-7    the polynomials' error in the f32 evaluation on |r| <= pi/2,
+//                 the final FMAs' roundings in it, as tools/fit_sky_polys.py
+//                 reports it (cos; sin 1.20e-7; a dense grid's maximum);
+//      5.96e-8    the reduction: r - j P1 is exact (x and j P1 are multiples
+//                 of a common power of two at most 2^24 of which they differ
+//                 by), r - j P2 rounds once, by <= ulp(r)/2 = 2^-24, |r| < 2;
+//      2.6e-12    + 1.63e-12 |x|: |j| (pi - P1 - P2), |j| <= |x| / pi + 1/2;
+//      2.9e-13 |x|  kInvPi is 1/pi (1 - 4.03e-8), so |r| passes pi/2 by up to
+//                 4.03e-8 |x| (0.085 at 2^21), where the cos fit's own error
+//                 grows from 7.1e-8 to 6.9e-7, convex: <= 7.2e-6 per unit;
+//    and |d sin|, |d cos| <= |d r|.  It stays under 2.5e-7 for |x| <= 2.0e4.
+//    Measured per binade on the GPU (profiles/transcendentals_exhaustive_gpu.txt):
+//    2.06e-7 in [4, 8), at x = -+7.85337734, the input at which an earlier
+//    "2e-7 on [-8, 2]" here was false; 2.14e-7 below 2^14, 3.56e-6 below 2^21.
+//  * |x| >= 2^21: the shifter holds no integer, r is not reduced: no bound.
+//    Nothing clamps lambda' before the call.  Unmasked lambda' of the fuzzed
+//    scenes (tests/test_transcendentals_host.py): within [-7, fl(pi/2)] in
+//    every converged scene; direct mode at steps near 3, where Newton's
+//    refinement does not converge, reaches tens of radians (57.5), far inside
+//    this bound's range.
 GEO_HD void sincos_sky_(float x, float* s, float* c) {
     constexpr float kShifter = 12582912.0f;  // 1.5 * 2^23
     const float tj = fmaf_(x, kInvPi, kShifter);
@@ -262,7 +312,7 @@ GEO_HD void sincos_sky_(float x, float* s, float* c) {
 // degree 6, and 1 - h for x < 0.  h <= 0.5 + 1 ulp, so the result is in
 // [0, 1] for every input.  No branch; 18 VALU.
 GEO_HD float acos_pi_(float x) {
-    const float a = __builtin_fminf(__builtin_fabsf(x), 1.0f);
+    const float a = min_nan_b_(__builtin_fabsf(x), 1.0f);
     const float s = sqrt_unit_(1.0f - a);
     float p = fmaf_(8.312922437e-04f, a, -3.820668207e-03f);
     p = fmaf_(p, a, 8.837061934e-03f);
@@ -278,7 +328,11 @@ GEO_HD float acos_pi_(float x) {
 // atan2f_'s reduction to |t| <= tan(pi/8) with its offsets in turns, a cubic
 // polynomial in t^2 with 1 / (2 pi) folded in, then the half-plane and
 // lower-half reflections (x < 0: 1/2 - r; y < 0: 1 - r).  atan2(+-0, 0) = 0;
-// a NaN y gives NaN (the caller's clamp maps it to 0).
+// a NaN y gives NaN (the caller's clamp maps it to 0), and so does a
+// denominator below 2^-128, whose reciprocal overflows (both |x| and |y|
+// denormal; the sky direction is of unit length).  <= 1e-7 on the circle for
+// max(|x|, |y|) in [2^-60, 2^60], measured 6.9e-8 over the sets of
+// tests/native/transcendentals_exhaustive.hip.
 GEO_HD float atan2_turns_(float y, float x) {
     const float ay = __builtin_fabsf(y);
     const float ax = __builtin_fabsf(x);
