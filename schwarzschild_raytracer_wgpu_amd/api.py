@@ -314,18 +314,18 @@ class Context:
         """geo_render_band_set_frames: len(frames) (1 .. GEO_MAX_BATCH_FRAMES) frames of one scene in one
         launch; frame f's packed bands at byte f*frame_stride of out_rgba (default: packed back to back).
         Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
-
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
+        n, arr, _, frame_stride = _batch_frames(frames, width, band_rows, nbands, out_rgba, frame_stride, steps_total)
         check("geo_render_band_set_frames", lib.geo_render_band_set_frames(
             self._h, arr, n, ctypes.byref(scene), width, height, band_rows, row0, row_stride, nbands,
+            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+
+    def _render_batch(self, name: str, frames, scenes, width: int, height: int, band_rows: int, row0: int,
+                      row_stride: int, nbands: int, out_rgba, frame_stride, steps_total, stream) -> None:
+        """A batched render through the library's `name` (geo_render_band_set_batch's prototype)."""
+        n, arr, sarr, frame_stride = _batch_frames(frames, width, band_rows, nbands, out_rgba, frame_stride,
+                                                   steps_total, scenes)
+        check(name, getattr(lib, name)(
+            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
             _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
 
     def render_disk_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int, row_stride: int,
@@ -335,23 +335,8 @@ class Context:
         shaded when set_disk_shift is on; frame f's packed bands at byte f*frame_stride of out_rgba (default:
         packed back to back).  scenes: one GeoScene for every frame, or one per frame (a moving observer: they
         may differ in r_obs only).  Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
-        scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
-        if len(scenes) != n:
-            raise ValueError("one scene, or one scene per frame")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
-
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
-        sarr = (GeoScene * n)(*scenes)
-        check("geo_render_disk_batch", lib.geo_render_disk_batch(
-            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
-            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+        self._render_batch("geo_render_disk_batch", frames, scenes, width, height, band_rows, row0, row_stride,
+                           nbands, out_rgba, frame_stride, steps_total, stream)
 
     def render_ss_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int, row_stride: int,
                         nbands: int, out_rgba, frame_stride: int | None = None, steps_total=None,
@@ -360,23 +345,8 @@ class Context:
         GEO_FLAG_DISK, or shaded when set_disk_shift is on); sizes, rows and bands in output pixels; frame f's
         packed bands at byte f*frame_stride of out_rgba (default: packed back to back).  scenes: one GeoScene for
         every frame, or one per frame (a moving observer: they may differ in r_obs only).  Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
-        scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
-        if len(scenes) != n:
-            raise ValueError("one scene, or one scene per frame")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
-
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
-        sarr = (GeoScene * n)(*scenes)
-        check("geo_render_ss_batch", lib.geo_render_ss_batch(
-            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
-            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+        self._render_batch("geo_render_ss_batch", frames, scenes, width, height, band_rows, row0, row_stride,
+                           nbands, out_rgba, frame_stride, steps_total, stream)
 
     def render_emission_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int,
                               row_stride: int, nbands: int, out_rgba, frame_stride: int | None = None,
@@ -386,23 +356,8 @@ class Context:
         rows and bands are then in output pixels); frame f's packed bands at byte f*frame_stride of out_rgba
         (default: packed back to back).  scenes: one GeoScene for every frame, or one per frame (a moving
         observer: they may differ in r_obs only).  Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
-        scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
-        if len(scenes) != n:
-            raise ValueError("one scene, or one scene per frame")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
-
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
-        sarr = (GeoScene * n)(*scenes)
-        check("geo_render_emission_batch", lib.geo_render_emission_batch(
-            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
-            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+        self._render_batch("geo_render_emission_batch", frames, scenes, width, height, band_rows, row0, row_stride,
+                           nbands, out_rgba, frame_stride, steps_total, stream)
 
     def render_disk_ring_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int,
                                row_stride: int, nbands: int, out_rgba, frame_stride: int | None = None,
@@ -413,23 +368,8 @@ class Context:
         bands are then in output pixels); frame f's packed bands at byte f*frame_stride of out_rgba (default:
         packed back to back).  scenes: one GeoScene for every frame, or one per frame (a moving observer: they
         may differ in r_obs only).  Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
-        scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
-        if len(scenes) != n:
-            raise ValueError("one scene, or one scene per frame")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
-
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
-        sarr = (GeoScene * n)(*scenes)
-        check("geo_render_disk_ring_batch", lib.geo_render_disk_ring_batch(
-            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
-            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+        self._render_batch("geo_render_disk_ring_batch", frames, scenes, width, height, band_rows, row0, row_stride,
+                           nbands, out_rgba, frame_stride, steps_total, stream)
 
     def render_bands(self, frame: GeoFrame, scene: GeoScene, width: int, height: int, band_rows: int, band0: int,
                      band_step: int, nbands: int, out_rgba, out_mask=None, out_uv=None, out_steps=None,
@@ -476,23 +416,27 @@ class Context:
         output pixels); frame f's packed bands at byte f*frame_stride of out_rgba (default: packed back to
         back).  scenes: one GeoScene for every frame, or one per frame (a moving observer: they may differ in
         r_obs only).  A one-sample frame is render_disk_adaptive's bit for bit.  Colour only."""
-        n = len(frames)
-        if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
-            raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
+        self._render_batch("geo_render_disk_adaptive_batch", frames, scenes, width, height, band_rows, row0, row_stride,
+                           nbands, out_rgba, frame_stride, steps_total, stream)
+
+
+def _batch_frames(frames, width: int, band_rows: int, nbands: int, out_rgba, frame_stride, steps_total, scenes=None):
+    """The checks every batched render shares; (the frame count, the frames and the scenes (one GeoScene for
+    every frame, or one per frame) as ctypes arrays, frame_stride)."""
+    n = len(frames)
+    if not 1 <= n <= _lib.GEO_MAX_BATCH_FRAMES:
+        raise ValueError(f"1 .. {_lib.GEO_MAX_BATCH_FRAMES} frames per batch")
+    if scenes is not None:
         scenes = [scenes] * n if isinstance(scenes, GeoScene) else list(scenes)
         if len(scenes) != n:
             raise ValueError("one scene, or one scene per frame")
-        fbytes = nbands * band_rows * width * 4
-        frame_stride = fbytes if frame_stride is None else frame_stride
-        import torch
+    fbytes = nbands * band_rows * width * 4
+    frame_stride = fbytes if frame_stride is None else frame_stride
+    import torch
 
-        _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
-        _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
-        arr = (GeoFrame * n)(*frames)
-        sarr = (GeoScene * n)(*scenes)
-        check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
-            self._h, arr, sarr, n, width, height, band_rows, row0, row_stride, nbands,
-            _ptr(out_rgba), frame_stride, _ptr(steps_total), _stream_handle(stream)))
+    _check_buffer("out_rgba", out_rgba, (n - 1) * frame_stride + fbytes)
+    _check_buffer("steps_total", steps_total, 8, (torch.int64, torch.uint64))
+    return n, (GeoFrame * n)(*frames), None if scenes is None else (GeoScene * n)(*scenes), frame_stride
 
 
 def _check_outputs(nrows: int, width: int, rgba, mask, uv, steps, steps_total) -> None:

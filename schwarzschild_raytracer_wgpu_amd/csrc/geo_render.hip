@@ -13,6 +13,10 @@
 
 #include "../../include/geo/geo.h"
 #include "geo_render_kernels.h"
+#include "geo_render_rules.h"
+
+static_assert(kRuleMaxFrames == kMaxBatchFrames && kRuleBandRowAlign == kBandRowAlign,
+              "the rules' limits are the kernels'");
 
 extern "C" {
 
@@ -714,57 +718,9 @@ static int invalid_call(geo_ctx* c) {
     return GEO_EINVAL;
 }
 
-// A render call as its entry point states it.
-struct RenderCall {
-    const geo_frame* frames;      // nframes uniforms (1 .. kMaxBatchFrames)
-    uint32_t nframes = 1;
-    size_t out_frame_stride = 0;  // frame f's output starts this many bytes after frame f - 1's
-    const geo_scene* scene;
-    // `scene` points at nframes scenes, frame f's at scene[f] (they may differ
-    // in r_obs only); otherwise one scene for every frame
-    bool scene_per_frame = false;
-    bool allow_disk = false;  // the entry point draws GEO_FLAG_DISK scenes
-    // geo_render_disk_batch (GEO_FLAG_DISK scenes, any nframes, through the
-    // batched disk kernel); the other entry points draw a disk frame alone
-    bool disk_batch = false;
-    // geo_render_ss_batch (GEO_FLAG_SS4 scenes, any nframes, through the
-    // batched SS kernels); the other entry points draw an SS frame alone
-    bool ss_batch = false;
-    // geo_render_emission_batch (GEO_FLAG_DISK scenes with the emission set,
-    // with GEO_FLAG_SS4 or without, any nframes, through the batched emission
-    // kernels); the other entry points draw an emission frame alone
-    bool emit_batch = false;
-    // geo_render_disk_ring_batch (GEO_FLAG_DISK scenes with geo_set_disk_ring_f64
-    // on, unshaded, shifted or with the emission, with GEO_FLAG_SS4 or without,
-    // any nframes, through the batched ring kernels); every other entry point
-    // refuses a batched or supersampled disk frame while the state is on
-    bool ring_batch = false;
-    // geo_render_disk_adaptive (GEO_FLAG_DISK scenes in GEO_MODE_ADAPTIVE, one
-    // frame, through the adaptive disk kernels); every other entry point
-    // refuses the disk in that mode
-    bool disk_adaptive = false;
-    // geo_render_disk_adaptive_batch (the same scenes, with GEO_FLAG_SS4 or
-    // without, any nframes, through the batched adaptive disk kernels)
-    bool adaptive_batch = false;
-    uint32_t width, height, row0, nrows, band_rows, band_stride;
-    uint8_t* out_rgba8;
-    uint8_t* out_mask = nullptr;  // (a batch draws colour only)
-    float* out_uv = nullptr;
-    uint32_t* out_steps = nullptr;
-    unsigned long long* steps_total;
-    void* stream;
-};
-
-// What the stages of a render call (render_impl) hand on.
-struct RenderWork {
-    float* out_hits;  // geo_disk_hits_next_render's buffer, geo_disk_shift_next_render's,
-    float* out_g;     // geo_disk_emission_next_render's
-    float* out_q;
-    bool emit;  // a GEO_FLAG_DISK scene with the emission set (check_scene)
-    bool disk, ring_flag, mips, adaptive, defer;  // what the scene asks for (check_scene)
-    bool ss;  // GEO_FLAG_SS4: the kernels' frame is the sample frame, twice the call's in width, height and rows
-    bool ring;                                    // ring_flag and a capture orbit to draw (fill_frames)
-    bool disk_ring;  // a disk frame with geo_set_disk_ring_f64 on and a capture orbit to draw (check_scene)
+// What the stages of a render call (render_impl) hand on: what the rules
+// decided (geo_render_rules.h) and what the launch needs.
+struct RenderWork : RenderRules {
     FrameK fk[kMaxBatchFrames];
     geo::PixelConsts pk[kMaxBatchFrames];
     RenderArgs a;
@@ -774,121 +730,23 @@ struct RenderWork {
     bool record;   // this render records its tiles' costs
 };
 
-// Stage 1: the rules a call must meet before anything is done for it, in the
-// order that decides which status a call breaking several of them gets.
-static int check_scene(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
-    const geo_scene* scene = rc.scene;
-    if (scene->mode != GEO_MODE_DIRECT && scene->mode != GEO_MODE_FAN && scene->mode != GEO_MODE_ADAPTIVE)
-        return GEO_EINVAL;
-    if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
-                          GEO_FLAG_DISK | GEO_FLAG_SS4)) != 0)
-        return GEO_EINVAL;
-    // geo_render_disk_adaptive draws GEO_MODE_ADAPTIVE disk scenes only, DISK
-    // with DEFER_STEPS at most (the older calls draw the direct and fan scenes)
-    if (rc.disk_adaptive &&
-        (scene->mode != GEO_MODE_ADAPTIVE || (scene->flags & ~GEO_FLAG_DEFER_STEPS) != GEO_FLAG_DISK))
-        return GEO_EINVAL;
-    // geo_render_disk_adaptive_batch likewise, with SS4 beside them
-    if (rc.adaptive_batch && (scene->mode != GEO_MODE_ADAPTIVE ||
-                              (scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != GEO_FLAG_DISK))
-        return GEO_EINVAL;
-    // GEO_FLAG_SS4 (every rule here, where the bit was refused as an unknown
-    // one before: a call that breaks an older rule too keeps its status): the
-    // one-frame entry points (the ones that draw a disk frame alone) and
-    // geo_render_ss_batch, direct mode, the level-0 sampler, colour only (an
-    // armed hit or g buffer, consumed by render_impl, refuses the call), DISK
-    // and DEFER_STEPS at most, and a sample frame of twice the size that the
-    // entry points take.  In the adaptive mode geo_render_disk_adaptive_batch
-    // alone takes the flag, by the same rules.
-    w.ss = (scene->flags & GEO_FLAG_SS4) != 0;
-    if (w.ss && (!rc.allow_disk || rc.disk_batch ||
-                 (!rc.ss_batch && !rc.emit_batch && !rc.ring_batch && !rc.adaptive_batch && rc.nframes != 1) ||
-                 scene->mode != (rc.adaptive_batch ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
-                 (scene->flags & ~(GEO_FLAG_SS4 | GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS)) != 0 || rc.out_mask ||
-                 rc.out_uv || rc.out_steps || w.out_hits || w.out_g || w.out_q || rc.width > (1u << 19) ||
-                 rc.height > (1u << 19)))
-        return GEO_EINVAL;
-    // geo_render_ss_batch draws SS4 scenes only (the other batched calls draw the rest)
-    if (rc.ss_batch && !w.ss) return GEO_EINVAL;
-    // GEO_FLAG_DISK: the one-frame entry points, geo_render_disk_batch and (with SS4) geo_render_ss_batch, direct
-    // mode, DEFER_STEPS at most
-    w.disk = (scene->flags & GEO_FLAG_DISK) != 0;
-    if (w.disk && (!rc.allow_disk ||
-                   scene->mode != (rc.disk_adaptive || rc.adaptive_batch ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT) ||
-                   (scene->flags & ~(GEO_FLAG_DISK | GEO_FLAG_DEFER_STEPS | GEO_FLAG_SS4)) != 0))
-        return GEO_EINVAL;
-    // geo_render_disk_batch draws disk scenes only, and colour only: an armed
-    // per-pixel buffer (consumed by render_impl) refuses the call
-    if (rc.disk_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
-    // geo_render_emission_batch likewise (all of its scenes with GEO_FLAG_SS4
-    // or none: fill_frames' rule that a batch's flags agree); without the
-    // emission set it has nothing to draw (GEO_ESTATE, after the disk's below)
-    if (rc.emit_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
-    // geo_render_disk_ring_batch likewise; with the state off it has nothing
-    // to draw (GEO_ESTATE, after the disk's below)
-    if (rc.ring_batch && (!w.disk || w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
-    // geo_render_disk_adaptive_batch likewise (its scenes are disk scenes by the rule above)
-    if (rc.adaptive_batch && (w.out_hits || w.out_g || w.out_q)) return GEO_EINVAL;
-    // geo_set_disk_emission: the one-frame entry points and geo_render_emission_batch
-    // (through the older batched calls a disk frame would come out without
-    // its emission: refused, nothing launched)
-    w.emit = w.disk && c->emit_set;
-    if (w.emit && (rc.disk_batch || rc.ss_batch)) return GEO_EINVAL;
-    // geo_set_disk_ring_f64: the one-frame entry points' per-pixel renders
-    // and geo_render_disk_ring_batch only (through any other call a
-    // supersampled or batched disk frame would come out without its band:
-    // refused, nothing launched; geo_render_disk_adaptive_batch has its rule
-    // below, with geo_render_disk_adaptive's: the state is ignored for rs = 0)
-    if (w.disk && c->disk_ring && !rc.ring_batch && !rc.adaptive_batch &&
-        (w.ss || rc.disk_batch || rc.ss_batch || rc.emit_batch))
-        return GEO_EINVAL;
-    // (no capture orbit, rs = 0: the state is ignored, the plain disk frame)
-    w.disk_ring = w.disk && c->disk_ring && scene->rs > 0.0f && scene->r_obs > scene->rs;
-    w.ring_flag = (scene->flags & GEO_FLAG_RING_F64) != 0;
-    if (w.ring_flag && (scene->mode == GEO_MODE_FAN || (scene->flags & (GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS)) != 0))
-        return GEO_EINVAL;
-    // frame-aligned 2 x 2 quads: the rows a wave covers start on even frame rows
-    w.mips = (scene->flags & GEO_FLAG_MIPS) != 0;
-    if (w.mips && ((rc.row0 | rc.band_stride) & 1u) != 0) return GEO_EINVAL;
-    if (rc.nframes == 0 || rc.nframes > kMaxBatchFrames) return GEO_EINVAL;
-    if (rc.nframes > 1 && (w.mips || rc.out_mask || rc.out_uv || rc.out_steps || rc.out_frame_stride % 4u != 0 ||
-                           rc.out_frame_stride < (size_t)rc.nrows * rc.width * 4u))
-        return GEO_EINVAL;
-    w.adaptive = scene->mode == GEO_MODE_ADAPTIVE;
-    // tol: 0 (default) or a positive finite tolerance in the adaptive mode, 0 otherwise
-    if (w.adaptive ? !(scene->tol >= 0.0f && scene->tol <= 3.0e38f) : scene->tol != 0.0f) return GEO_EINVAL;
-    w.defer = (scene->flags & GEO_FLAG_DEFER_STEPS) != 0;
-    if (scene->max_steps > (1u << 24)) return GEO_EINVAL;  // a wave's step sum must fit u32
-    if (w.defer && rc.steps_total) return GEO_EINVAL;
-    if (!c->sky) return GEO_ESTATE;
-    if (scene->mode == GEO_MODE_FAN && (c->fan_cur < 0 || c->n_fan[c->fan_cur] < 2)) return GEO_ESTATE;
-    // bound > 0 (escape test folding, geo_pixel.h) needs r_obs > 0 and sphere_r > 0
-    if (scene->mode != GEO_MODE_FAN &&
-        (!(scene->step > 0.0f) || !(scene->r_obs > 0.0f) || !(scene->sphere_r > 0.0f) || !(scene->rs >= 0.0f)))
-        return GEO_EINVAL;
-    if (w.disk) {
-        if (!c->disk_set) return GEO_ESTATE;
-        if (rc.emit_batch && !c->emit_set) return GEO_ESTATE;
-        if (rc.ring_batch && !c->disk_ring) return GEO_ESTATE;
-        if (!(scene->rs == 0.0f || (scene->r_obs > scene->rs && scene->rs < c->disk.r_in)) ||
-            !(c->disk.r_out < scene->sphere_r) || !(scene->r_obs < scene->sphere_r))
-            return GEO_EINVAL;
-        // shading: circular timelike orbits down to the inner edge
-        if ((c->shift_set || c->emit_set) && scene->rs > 0.0f && !(c->disk.r_in > 1.5f * scene->rs))
-            return GEO_EINVAL;
-        // geo_render_disk_adaptive with geo_set_disk_ring_f64 on and a capture
-        // orbit to draw: the frame would come out without its band
-        // (geo_render_disk_adaptive_batch too: its frames share rs, and each
-        // observer is outside the horizon by fill_frames' rule)
-        if ((rc.disk_adaptive || rc.adaptive_batch) && w.disk_ring) return GEO_EINVAL;
-    }
-    return GEO_OK;
+// What the rules read of the context.
+static RuleState rule_state(const geo_ctx* c) {
+    RuleState s;
+    s.sky = c->sky != nullptr;
+    s.n_fan = c->fan_cur < 0 ? 0u : c->n_fan[c->fan_cur];
+    s.disk_set = c->disk_set;
+    s.shift_set = c->shift_set;
+    s.emit_set = c->emit_set;
+    s.disk_ring = c->disk_ring;
+    s.r_in = c->disk.r_in;
+    s.r_out = c->disk.r_out;
+    return s;
 }
 
 // Stage 1, per frame: its camera and scene constants, and the rules by which
-// the frames of a batch must agree.
+// the frames of a batch must agree (check_frames).
 static int fill_frames(const RenderCall& rc, RenderWork& w) {
-    const geo_scene* scene = rc.scene;
     for (uint32_t i = 0; i < rc.nframes; ++i) {
         const geo_frame& fr = rc.frames[i];
         std::memcpy(&w.fk[i].frame, &fr, sizeof(geo_frame));
@@ -897,33 +755,8 @@ static int fill_frames(const RenderCall& rc, RenderWork& w) {
         w.fk[i].cam = geo::camera_consts(fr.display_to_movement, fr.movement_to_central, ssf * rc.width,
                                          ssf * rc.height);
         w.fk[i].kt = geo::aberration_kt(fr.psi_factor_and_position[0]);
-        const geo_scene& si = rc.scene_per_frame ? scene[i] : *scene;
-        if (i > 0 && rc.scene_per_frame) {
-            // one launch, one sampler, one integration: every field but r_obs
-            // agrees with frame 0's (a fan-mode batch draws one fan: r_obs too)
-            if (si.rs != scene->rs || si.sphere_r != scene->sphere_r || si.step != scene->step ||
-                si.max_steps != scene->max_steps || si.mode != scene->mode || si.flags != scene->flags ||
-                si.tol != scene->tol || (scene->mode == GEO_MODE_FAN && si.r_obs != scene->r_obs) ||
-                !(si.r_obs > 0.0f))
-                return GEO_EINVAL;
-        }
-        // GEO_FLAG_DISK's rules for this frame's observer (frame 0's in check_scene)
-        if (w.disk && i > 0 && (!(si.rs == 0.0f || si.r_obs > si.rs) || !(si.r_obs < si.sphere_r)))
-            return GEO_EINVAL;
-        // geo_set_disk_ring_f64 in a batch (geo_render_disk_ring_batch): the
-        // frames share rs and each has passed the rule above, so frame 0's
-        // w.disk_ring (rs > 0 and r_obs > rs: a capture orbit to draw) holds
-        // for every frame; each gets band constants of its own (launch_ring_frames)
-        w.pk[i] = geo::make_consts(si.rs, si.sphere_r, si.r_obs, si.step, si.max_steps, si.tol);
-        if (geo::geodesic_kind(w.pk[i]) != geo::geodesic_kind(w.pk[0])) return GEO_EINVAL;
     }
-    // GEO_FLAG_RING_F64 (geo_band.h): the band's lanes take the f64 path; no
-    // capture orbit (rs = 0, or the observer inside the horizon): the plain draw
-    w.ring = w.ring_flag && scene->rs > 0.0f && scene->r_obs > scene->rs;
-    if (w.ring_flag && rc.scene_per_frame)  // a batch: any frame with a capture orbit (each gets its own factor)
-        for (uint32_t i = 1; i < rc.nframes; ++i)
-            w.ring = w.ring || (scene[i].rs > 0.0f && scene[i].r_obs > scene[i].rs);
-    return GEO_OK;
+    return check_frames(rc, w, w.pk);
 }
 
 // Stage 2: the kernels' arguments (the sky and its mip chain, the fan, the
@@ -1181,7 +1014,7 @@ static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderW
     std::memset(&db, 0, sizeof(db));
     if (eb) std::memset(eb, 0, sizeof(*eb));
     for (uint32_t i = 0; i < rc.nframes; ++i) {
-        const geo_scene& si = rc.scene_per_frame ? rc.scene[i] : *rc.scene;
+        const geo_scene& si = traits(rc.entry).scene_per_frame ? rc.scene[i] : *rc.scene;
         DiskFrameK& f = db.f[i];
         geo::DiskConsts dk;
         if (!geo::disk_consts(rc.frames[i].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out,
@@ -1313,8 +1146,8 @@ static int launch_ring_frames(geo_ctx* c, const RenderCall& rc, const RenderWork
     std::memset(&bt, 0, sizeof(bt));
     const uint32_t ssf = w.ss ? 2u : 1u;
     for (uint32_t i = 0; i < rc.nframes; ++i)
-        bt.k[i] = geo::band_consts(rc.frames[i], rc.scene_per_frame ? rc.scene[i] : *rc.scene, ssf * rc.width,
-                                   ssf * rc.height);
+        bt.k[i] = geo::band_consts(rc.frames[i], traits(rc.entry).scene_per_frame ? rc.scene[i] : *rc.scene,
+                                   ssf * rc.width, ssf * rc.height);
     void*& table = c->band_table[w.slot];
     if (!table && hipMalloc(&table, sizeof(BandTable)) != hipSuccess) {
         table = nullptr;
@@ -1384,17 +1217,17 @@ static int launch_adaptive_frames(const geo_ctx* c, const RenderCall& rc, const 
 
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    if (rc.adaptive_batch) return launch_adaptive_frames(c, rc, w);
-    if (rc.ring_batch) {
-        // (no capture orbit, rs = 0: the state is ignored, the older batches' kernels)
-        if (w.disk_ring) return launch_ring_frames(c, rc, w);
-        if (w.emit) return launch_emit_frames(c, rc, w);
-        return w.ss ? launch_ss_frames(c, rc, w) : launch_disk_frames(c, rc, w);
+    switch (choose_launcher(rc, w)) {
+        case Launcher::kAdaptiveFrames: return launch_adaptive_frames(c, rc, w);
+        case Launcher::kRingFrames: return launch_ring_frames(c, rc, w);
+        case Launcher::kEmitFrames: return launch_emit_frames(c, rc, w);
+        case Launcher::kSsFrames: return launch_ss_frames(c, rc, w);
+        case Launcher::kDiskFrames: return launch_disk_frames(c, rc, w);
+        case Launcher::kSsFrame: return launch_ss_frame(c, rc, w);
+        case Launcher::kDiskFrame: return launch_disk_frame(c, rc, w);
+        case Launcher::kFan: return launch_fan(c, rc, w);
+        case Launcher::kFrames: break;
     }
-    if (rc.emit_batch) return launch_emit_frames(c, rc, w);
-    if (w.ss) return rc.ss_batch ? launch_ss_frames(c, rc, w) : launch_ss_frame(c, rc, w);
-    if (w.disk) return rc.disk_batch ? launch_disk_frames(c, rc, w) : launch_disk_frame(c, rc, w);
-    if (rc.scene->mode == GEO_MODE_FAN) return launch_fan(c, rc, w);
     geo::BandConsts band_k;  // (one frame; a batch derives its frames' constants on the device)
     if (w.ring && rc.nframes == 1) band_k = geo::band_consts(rc.frames[0], *rc.scene, rc.width, rc.height);
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
@@ -1459,7 +1292,7 @@ static int render_impl(geo_ctx* c, const RenderCall& rc) {
     c->g_next = nullptr;
     w.out_q = c->q_next;
     c->q_next = nullptr;
-    int st = check_scene(c, rc, w);
+    int st = check_scene(rule_state(c), rc, w);
     if (st) return st;
     DeviceGuard g(c->device);
     if (!g.ok) return GEO_EHIP;
@@ -1669,229 +1502,84 @@ int geo_set_tile_order(geo_ctx* c, uint32_t tiles_x, uint32_t tiles_y, const uin
     return GEO_OK;
 }
 
-// What every entry point's call has: nrows rows from row0 on in bands of
-// band_rows rows band_stride apart, colour only, one frame, one scene, no
-// disk; each entry point adds what it has beyond that.
-static RenderCall render_call(const geo_frame* frames, const geo_scene* scene, uint32_t width, uint32_t height,
-                              uint32_t row0, uint32_t nrows, uint32_t band_rows, uint32_t band_stride,
-                              uint8_t* out_rgba8, unsigned long long* steps_total, void* stream) {
+// The one-frame entry points: the argument stage (frame_call; g0 .. g3 are the
+// entry point's own row arguments), then the render.
+static int render_frame(Entry e, geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
+                        uint32_t height, uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3, uint8_t* out_rgba8,
+                        uint8_t* out_mask, float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                        void* stream) {
     RenderCall rc;
-    rc.frames = frames;
-    rc.scene = scene;
-    rc.width = width;
-    rc.height = height;
-    rc.row0 = row0;
-    rc.nrows = nrows;
-    rc.band_rows = band_rows;
-    rc.band_stride = band_stride;
-    rc.out_rgba8 = out_rgba8;
-    rc.steps_total = steps_total;
-    rc.stream = stream;
-    return rc;
-}
-
-int geo_render_rows(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
-                    uint32_t height, uint32_t row0, uint32_t nrows, uint8_t* out_rgba8,
-                    uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
-                    unsigned long long* steps_total, void* stream) {
-    if (!c || !frame || !scene || !out_rgba8 || width == 0 || height == 0 || nrows == 0)
+    if (!frame_call(rc, e, c, frame, scene, width, height, g0, g1, g2, g3, out_rgba8, out_mask, out_uv, out_steps,
+                    steps_total, stream))
         return invalid_call(c);
-    if ((uint64_t)row0 + nrows > height || width > (1u << 20) || height > (1u << 20))
-        return invalid_call(c);
-    // one band covering every row (2^21 >= nrows)
-    RenderCall rc = render_call(frame, scene, width, height, row0, nrows, 1u << 21, 1u << 21, out_rgba8, steps_total,
-                                stream);
-    rc.allow_disk = true;
-    rc.out_mask = out_mask;
-    rc.out_uv = out_uv;
-    rc.out_steps = out_steps;
     return render_impl(c, rc);
 }
 
-int geo_render_bands(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
-                     uint32_t height, uint32_t band_rows, uint32_t band0, uint32_t band_step,
-                     uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
-                     uint32_t* out_steps, unsigned long long* steps_total, void* stream) {
-    if (!c || !frame || !scene || !out_rgba8 || width == 0 || height == 0 || band_rows == 0 ||
-        nbands == 0 || band_step == 0 || band_rows < kBandRowAlign || (band_rows & (band_rows - 1)) != 0)
+// The batched entry points likewise (batch_call).
+static int render_batch(Entry e, geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
+                        uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                        uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride, unsigned long long* steps_total,
+                        void* stream) {
+    RenderCall rc;
+    if (!batch_call(rc, e, c, frames, scenes, nframes, width, height, band_rows, row0, row_stride, nbands, out_rgba8,
+                    out_frame_stride, steps_total, stream))
         return invalid_call(c);
-    if (width > (1u << 20) || height > (1u << 20)) return invalid_call(c);
-    const uint64_t first = (uint64_t)band0 * band_rows;
-    const uint64_t last = first + (uint64_t)(nbands - 1) * band_step * band_rows;
-    const uint64_t nrows = (uint64_t)nbands * band_rows;
-    if (first >= height || last >= height || nrows > (1u << 20)) return invalid_call(c);
-    RenderCall rc = render_call(frame, scene, width, height, (uint32_t)first, (uint32_t)nrows, band_rows,
-                                band_step * band_rows, out_rgba8, steps_total, stream);
-    rc.allow_disk = true;
-    rc.out_mask = out_mask;
-    rc.out_uv = out_uv;
-    rc.out_steps = out_steps;
     return render_impl(c, rc);
 }
 
-// The band set's arguments, checked (geo_render_band_set, geo_render_band_set_frames).
-static bool band_set_ok(uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
-                        uint32_t nbands) {
-    // band_rows: a multiple of 8, at most 4096 unless a power of two (band_rows_magic)
-    if (width == 0 || height == 0 || band_rows == 0 || nbands == 0 || row_stride < band_rows ||
-        band_rows % kBandRowAlign != 0 || ((band_rows & (band_rows - 1)) != 0 && band_rows > 4096u))
-        return false;
-    if (width > (1u << 20) || height > (1u << 20)) return false;
-    const uint64_t last = (uint64_t)row0 + (uint64_t)(nbands - 1) * row_stride;
-    const uint64_t nrows = (uint64_t)nbands * band_rows;
-    return row0 < height && last < height && nrows <= (1u << 20);
+int geo_render_rows(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width, uint32_t height,
+                    uint32_t row0, uint32_t nrows, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
+                    uint32_t* out_steps, unsigned long long* steps_total, void* stream) {
+    return render_frame(Entry::kRows, c, frame, scene, width, height, row0, nrows, 0, 0, out_rgba8, out_mask, out_uv,
+                        out_steps, steps_total, stream);
 }
 
-int geo_render_band_set(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
-                        uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride, uint32_t nbands,
-                        uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
-                        unsigned long long* steps_total, void* stream) {
-    if (!c || !frame || !scene || !out_rgba8 || !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frame, scene, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.allow_disk = true;
-    rc.out_mask = out_mask;
-    rc.out_uv = out_uv;
-    rc.out_steps = out_steps;
-    return render_impl(c, rc);
+int geo_render_bands(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width, uint32_t height,
+                     uint32_t band_rows, uint32_t band0, uint32_t band_step, uint32_t nbands, uint8_t* out_rgba8,
+                     uint8_t* out_mask, float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                     void* stream) {
+    return render_frame(Entry::kBands, c, frame, scene, width, height, band_rows, band0, band_step, nbands, out_rgba8,
+                        out_mask, out_uv, out_steps, steps_total, stream);
+}
+
+int geo_render_band_set(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width, uint32_t height,
+                        uint32_t band_rows, uint32_t row0, uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8,
+                        uint8_t* out_mask, float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                        void* stream) {
+    return render_frame(Entry::kBandSet, c, frame, scene, width, height, band_rows, row0, row_stride, nbands,
+                        out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
 }
 
 int geo_render_disk_adaptive(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
                              uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride, uint32_t nbands,
                              uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
                              unsigned long long* steps_total, void* stream) {
-    // a row range is the one-band case: any number of rows, as one band that
-    // covers them all (geo_render_rows' mapping; row_stride is not read)
-    const bool rows = nbands == 1 && band_rows != 0 && band_rows <= (1u << 20) && width != 0 && height != 0 &&
-                      width <= (1u << 20) && height <= (1u << 20) && row0 < height;
-    if (!c || !frame || !scene || !out_rgba8 ||
-        (!rows && !band_set_ok(width, height, band_rows, row0, row_stride, nbands)))
-        return invalid_call(c);
-    RenderCall rc = nbands == 1 ? render_call(frame, scene, width, height, row0, band_rows, 1u << 21, 1u << 21,
-                                              out_rgba8, steps_total, stream)
-                                : render_call(frame, scene, width, height, row0, nbands * band_rows, band_rows,
-                                              row_stride, out_rgba8, steps_total, stream);
-    rc.allow_disk = true;
-    rc.disk_adaptive = true;
-    rc.out_mask = out_mask;
-    rc.out_uv = out_uv;
-    rc.out_steps = out_steps;
-    return render_impl(c, rc);
-}
-
-int geo_render_disk_adaptive_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                                   uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
-                                   uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                                   unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    rc.allow_disk = true;
-    rc.adaptive_batch = true;
-    return render_impl(c, rc);
+    return render_frame(Entry::kDiskAdaptive, c, frame, scene, width, height, band_rows, row0, row_stride, nbands,
+                        out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
 }
 
 int geo_render_band_set_frames(geo_ctx* c, const geo_frame* frames, uint32_t nframes, const geo_scene* scene,
-                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
-                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
+                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                               uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                                unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scene || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scene, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    return render_impl(c, rc);
+    return render_batch(Entry::kBandSetFrames, c, frames, scene, nframes, width, height, band_rows, row0, row_stride,
+                        nbands, out_rgba8, out_frame_stride, steps_total, stream);
 }
 
-int geo_render_band_set_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                              uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
-                              uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                              unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    return render_impl(c, rc);
-}
-
-int geo_render_disk_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                          uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
-                          uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                          unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    rc.allow_disk = true;
-    rc.disk_batch = true;
-    return render_impl(c, rc);
-}
-
-int geo_render_ss_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                        uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
-                        uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                        unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    rc.allow_disk = true;
-    rc.ss_batch = true;
-    return render_impl(c, rc);
-}
-
-int geo_render_emission_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                              uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
-                              uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                              unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    rc.allow_disk = true;
-    rc.emit_batch = true;
-    return render_impl(c, rc);
-}
-
-int geo_render_disk_ring_batch(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
-                               uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
-                               uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
-                               unsigned long long* steps_total, void* stream) {
-    if (!c || !frames || !scenes || !out_rgba8 || nframes == 0 || nframes > kMaxBatchFrames ||
-        !band_set_ok(width, height, band_rows, row0, row_stride, nbands))
-        return invalid_call(c);
-    RenderCall rc = render_call(frames, scenes, width, height, row0, nbands * band_rows, band_rows, row_stride,
-                                out_rgba8, steps_total, stream);
-    rc.nframes = nframes;
-    rc.out_frame_stride = out_frame_stride;
-    rc.scene_per_frame = true;
-    rc.allow_disk = true;
-    rc.ring_batch = true;
-    return render_impl(c, rc);
-}
+// The batched entry points of geo_render_band_set_batch's prototype: scenes[f] belongs to frames[f].
+#define GEO_BATCH_ENTRY(name, entry)                                                                                 \
+    int name(geo_ctx* c, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes, uint32_t width,        \
+             uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride, uint32_t nbands,              \
+             uint8_t* out_rgba8, size_t out_frame_stride, unsigned long long* steps_total, void* stream) {          \
+        return render_batch(entry, c, frames, scenes, nframes, width, height, band_rows, row0, row_stride, nbands,  \
+                            out_rgba8, out_frame_stride, steps_total, stream);                                      \
+    }
+GEO_BATCH_ENTRY(geo_render_band_set_batch, Entry::kBandSetBatch)
+GEO_BATCH_ENTRY(geo_render_disk_batch, Entry::kDiskBatch)
+GEO_BATCH_ENTRY(geo_render_ss_batch, Entry::kSsBatch)
+GEO_BATCH_ENTRY(geo_render_emission_batch, Entry::kEmissionBatch)
+GEO_BATCH_ENTRY(geo_render_disk_ring_batch, Entry::kDiskRingBatch)
+GEO_BATCH_ENTRY(geo_render_disk_adaptive_batch, Entry::kDiskAdaptiveBatch)
+#undef GEO_BATCH_ENTRY
 
 }  // extern "C"

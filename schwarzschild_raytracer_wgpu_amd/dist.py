@@ -178,6 +178,60 @@ def _batch_key(scene) -> bytes:
     return bytes(b)
 
 
+def _adaptive_disk(scene) -> bool:
+    """A GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene: every older call refuses it, so it is routed by what it shows."""
+    from ._lib import GEO_FLAG_DISK, GEO_MODE_ADAPTIVE
+
+    return scene.mode == GEO_MODE_ADAPTIVE and bool(scene.flags & GEO_FLAG_DISK)
+
+
+def _refuse_adaptive_ring(scene, ring_f64: bool) -> None:
+    """No call draws the adaptive disk's f64 band: refused by name, not by the launch's GEO_EINVAL."""
+    if scene.rs > 0 and ring_f64:
+        raise ValueError("a GEO_MODE_ADAPTIVE disk scene cannot be drawn with set_disk_ring_f64 on: "
+                         "geo_render_disk_adaptive and geo_render_disk_adaptive_batch draw no f64 band; use "
+                         "set_disk_ring_f64(False), or GEO_MODE_DIRECT")
+
+
+def frame_entry(scene, ring_f64: bool) -> str:
+    """The library function that draws `scene` one frame at a time: geo_render_band_set, or for the adaptive
+    disk geo_render_disk_adaptive (with GEO_FLAG_SS4, which has no one-frame call, the batched one with one
+    frame).  ring_f64: the context's set_disk_ring_f64 state."""
+    from ._lib import GEO_FLAG_SS4
+
+    if not _adaptive_disk(scene):
+        return "geo_render_band_set"
+    _refuse_adaptive_ring(scene, ring_f64)
+    return "geo_render_disk_adaptive_batch" if scene.flags & GEO_FLAG_SS4 else "geo_render_disk_adaptive"
+
+
+def batch_entry(scene, emission_set: bool, ring_f64: bool, emission_batch: bool, disk_ring_batch: bool) -> str:
+    """The library function that draws a batch of `scene`'s frames in one launch.  emission_set, ring_f64: the
+    context's states; emission_batch, disk_ring_batch: ShardedFrame's keywords, without which a disk scene in
+    that state is refused here, by name, as the older batched entry points refuse it with GEO_EINVAL."""
+    from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4
+
+    if _adaptive_disk(scene):  # (with GEO_FLAG_SS4 or without, any shading, no keyword)
+        _refuse_adaptive_ring(scene, ring_f64)
+        return "geo_render_disk_adaptive_batch"
+    disk = bool(scene.flags & GEO_FLAG_DISK)
+    if disk and ring_f64:  # (with GEO_FLAG_SS4 or without, any shading: emission_batch is not needed)
+        if not disk_ring_batch:
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_ring_f64 on through the older "
+                             "batched entry points: pass disk_ring_batch=True (geo_render_disk_ring_batch), or use "
+                             "batch_launch=False, or set_disk_ring_f64(False)")
+        return "geo_render_disk_ring_batch"
+    if disk and emission_set:  # (with GEO_FLAG_SS4 or without)
+        if not emission_batch:
+            raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on through the older batched "
+                             "entry points: pass emission_batch=True (geo_render_emission_batch), or use "
+                             "batch_launch=False, or clear_disk_emission()")
+        return "geo_render_emission_batch"
+    if scene.flags & GEO_FLAG_SS4:
+        return "geo_render_ss_batch"
+    return "geo_render_disk_batch" if disk else "geo_render_band_set_batch"
+
+
 def _empty_timing(events, stream: int) -> None:
     """A timed step of a rank with no rows renders nothing: record the
     caller's pair back to back on the stream, so elapsed_time reads ~0
@@ -267,10 +321,13 @@ class ShardedFrame:
         self.disk_ring_batch = bool(disk_ring_batch)
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
-        self._refuse_adaptive_ring(scene)
-        if self.batch and not self._adaptive_disk_scene(scene):
-            self._refuse_ring_batch(scene)
-            self._refuse_emission_batch(scene)
+        from ._lib import GEO_MODE_ADAPTIVE
+
+        self._adaptive = GEO_MODE_ADAPTIVE
+        if self.batch:  # (a scene its path cannot draw is refused here, by name)
+            self._batch_entry(scene)
+        else:
+            frame_entry(scene, self._ring_f64())
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
         self.pending_scenes = []     # and copies of their scenes (they differ in r_obs at most)
         self._pending_key = b""
@@ -341,14 +398,11 @@ class ShardedFrame:
         if L.nbands() == 0:  # a frame too small to give this rank a band
             return
         sc = self.scene if scene is None else scene
-        if self._adaptive_disk_scene(sc):
-            self._refuse_adaptive_ring(sc)
-            self.ctx.render_disk_adaptive(self.frame if frame is None else frame, sc, self.width, self.height,
-                                          L.band_height(), L.row0(), L.cycle_rows, L.nbands(), buf, **outs)
-            return
-        self.ctx.render_band_set(self.frame if frame is None else frame, self.scene if scene is None else scene,
-                                 self.width, self.height, L.band_height(), L.row0(), L.cycle_rows, L.nbands(), buf,
-                                 **outs)
+        # (a supersampled adaptive disk scene has no one-frame call with these outputs: the library refuses it)
+        adaptive = frame_entry(sc, self._ring_f64()) != "geo_render_band_set"
+        render = self.ctx.render_disk_adaptive if adaptive else self.ctx.render_band_set
+        render(self.frame if frame is None else frame, sc, self.width, self.height, L.band_height(), L.row0(),
+               L.cycle_rows, L.nbands(), buf, **outs)
 
     def _assemble(self, b: int, src, n: int, stream=None) -> None:
         """Rank 0: frames of batch b from its own bands (bufs[b]) and the peers' gathered blocks."""
@@ -361,59 +415,12 @@ class ShardedFrame:
         k = (i // self.K) % 2 % self.S if self.batch else i % self.S
         return self.stream0 if k == 0 else self.extra[k - 1]
 
-    def _emission_scene(self, scene) -> bool:
-        """A GEO_FLAG_DISK scene of a context with the emission set."""
-        from ._lib import GEO_FLAG_DISK
+    def _ring_f64(self) -> bool:
+        return getattr(self.ctx, "disk_ring_f64", False)
 
-        return bool(scene is not None and scene.flags & GEO_FLAG_DISK
-                    and getattr(self.ctx, "disk_emission_set", False))
-
-    def _ring_scene(self, scene) -> bool:
-        """A GEO_FLAG_DISK scene of a context with set_disk_ring_f64 on."""
-        from ._lib import GEO_FLAG_DISK
-
-        return bool(scene is not None and scene.flags & GEO_FLAG_DISK and getattr(self.ctx, "disk_ring_f64", False))
-
-    @staticmethod
-    def _adaptive_disk_scene(scene) -> bool:
-        """A GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene: geo_render_disk_adaptive's
-        and geo_render_disk_adaptive_batch's, which every older call refuses."""
-        from ._lib import GEO_FLAG_DISK, GEO_MODE_ADAPTIVE
-
-        return bool(scene is not None and scene.mode == GEO_MODE_ADAPTIVE and scene.flags & GEO_FLAG_DISK)
-
-    def _refuse_adaptive_ring(self, scene) -> None:
-        """No call draws the adaptive disk's f64 band (geo_set_disk_ring_f64,
-        geo.h): a GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene with a capture orbit
-        (rs > 0) of a context with set_disk_ring_f64 on is refused here, by
-        name, instead of by the launch's GEO_EINVAL."""
-        if self._adaptive_disk_scene(scene) and scene.rs > 0 and getattr(self.ctx, "disk_ring_f64", False):
-            raise ValueError("a GEO_MODE_ADAPTIVE disk scene cannot be drawn with set_disk_ring_f64 on: "
-                             "geo_render_disk_adaptive and geo_render_disk_adaptive_batch draw no f64 band; use "
-                             "set_disk_ring_f64(False), or GEO_MODE_DIRECT")
-
-    def _refuse_emission_batch(self, scene) -> None:
-        """The older batched entry points draw no emission frames
-        (geo_set_disk_emission, geo.h): without emission_batch a GEO_FLAG_DISK
-        scene of a context with the emission set is refused here, by name,
-        instead of by the launch's GEO_EINVAL.  (With disk_ring_batch a ring
-        scene goes to geo_render_disk_ring_batch, which draws the emission.)"""
-        if self.disk_ring_batch and self._ring_scene(scene):
-            return
-        if not self.emission_batch and self._emission_scene(scene):
-            raise ValueError("batch_launch=True cannot draw a disk with set_disk_emission on through the older batched "
-                             "entry points: pass emission_batch=True (geo_render_emission_batch), or use "
-                             "batch_launch=False, or clear_disk_emission()")
-
-    def _refuse_ring_batch(self, scene) -> None:
-        """Only geo_render_disk_ring_batch draws a batched disk frame's f64
-        band (geo_set_disk_ring_f64, geo.h): without disk_ring_batch a
-        GEO_FLAG_DISK scene of a context with set_disk_ring_f64 on is refused
-        here, by name, instead of by the launch's GEO_EINVAL."""
-        if not self.disk_ring_batch and self._ring_scene(scene):
-            raise ValueError("batch_launch=True cannot draw a disk with set_disk_ring_f64 on through the older "
-                             "batched entry points: pass disk_ring_batch=True (geo_render_disk_ring_batch), or use "
-                             "batch_launch=False, or set_disk_ring_f64(False)")
+    def _batch_entry(self, scene) -> str:
+        return batch_entry(scene, getattr(self.ctx, "disk_emission_set", False), self._ring_f64(),
+                           self.emission_batch, self.disk_ring_batch)
 
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
@@ -428,7 +435,7 @@ class ShardedFrame:
         keyword), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
-        from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4, GeoFrame, GeoScene, check
+        from ._lib import GeoFrame, GeoScene, check
 
         band_h, row0, cycle, nb = self._band
         sh = self._sh[b % self.S] if stream is None else stream
@@ -447,24 +454,7 @@ class ShardedFrame:
         # supersampled scenes (with a disk or without) and thin-disk scenes
         # have batched entry points of their own (_batch_key keeps a launch's
         # flags equal)
-        adaptive_disk = self._adaptive_disk_scene(scenes[0])
-        if adaptive_disk:  # (every older call refuses it: routed by what the scene shows)
-            self._refuse_adaptive_ring(scenes[0])
-        else:
-            self._refuse_ring_batch(scenes[0])
-            self._refuse_emission_batch(scenes[0])
-        if adaptive_disk:
-            name = "geo_render_disk_adaptive_batch"  # (with GEO_FLAG_SS4 or without, any shading)
-        elif self.disk_ring_batch and self._ring_scene(scenes[0]):
-            name = "geo_render_disk_ring_batch"  # (with GEO_FLAG_SS4 or without, any shading)
-        elif self.emission_batch and self._emission_scene(scenes[0]):
-            name = "geo_render_emission_batch"  # (with GEO_FLAG_SS4 or without)
-        elif scenes[0].flags & GEO_FLAG_SS4:
-            name = "geo_render_ss_batch"
-        elif scenes[0].flags & GEO_FLAG_DISK:
-            name = "geo_render_disk_batch"
-        else:
-            name = "geo_render_band_set_batch"
+        name = self._batch_entry(scenes[0])
         st = getattr(self.lib, name)(
             self._ctx_h, self._frame_arr, self._scene_arr, n, self.width, self.height, band_h, row0, cycle, nb,
             self._lv[b][first], self.slice, None, sh)
@@ -619,21 +609,14 @@ class ShardedFrame:
             fref = self._frame_ref if frame is None else ctypes.byref(frame)
             sref = self._scene_ref if scene is None else ctypes.byref(scene)
             total = None if steps_total is None else steps_total.data_ptr()
-            if sc.mode == 2 and sc.flags & 16:  # GEO_MODE_ADAPTIVE | GEO_FLAG_DISK (_adaptive_disk_scene)
-                self._refuse_adaptive_ring(sc)
-                if sc.flags & 32:  # GEO_FLAG_SS4
-                    name = "geo_render_disk_adaptive_batch"
-                    st = lib.geo_render_disk_adaptive_batch(
-                        self._ctx_h, fref, sref, 1, self.width, self.height, band_h, row0, cycle, nb,
-                        self._lv[b][sub], self.slice, total, sh)
-                else:
-                    name = "geo_render_disk_adaptive"
-                    st = lib.geo_render_disk_adaptive(
-                        self._ctx_h, fref, sref, self.width, self.height, band_h, row0, cycle, nb, self._lv[b][sub],
-                        None, None, None, total, sh)
+            # (the hot path reads one field: only an adaptive scene can be the adaptive disk's)
+            name = "geo_render_band_set" if sc.mode != self._adaptive else frame_entry(sc, self._ring_f64())
+            if name == "geo_render_disk_adaptive_batch":
+                st = lib.geo_render_disk_adaptive_batch(
+                    self._ctx_h, fref, sref, 1, self.width, self.height, band_h, row0, cycle, nb,
+                    self._lv[b][sub], self.slice, total, sh)
             else:
-                name = "geo_render_band_set"
-                st = lib.geo_render_band_set(
+                st = getattr(lib, name)(
                     self._ctx_h, fref, sref, self.width, self.height, band_h, row0, cycle, nb, self._lv[b][sub], None,
                     None, None, total, sh)
             if st != 0:
