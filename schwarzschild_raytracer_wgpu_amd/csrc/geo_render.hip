@@ -606,69 +606,29 @@ static void fill_disk_tex(const geo_ctx* c, D& d) {
     d.tex_bytes = c->disk_bytes;
 }
 
-// A GEO_FLAG_DISK frame on the wave-block grid: geo_render_disk_kernel, or the
-// shifted render (geo_render_disk_shift_kernel) with its constants *sh, or the
-// emission render (geo_render_disk_emit_kernel) with *em.
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskShiftArgs) <= 4096,
-              "kernel arguments fit 4 KiB");
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskEmitArgs) <= 4096,
-              "kernel arguments fit 4 KiB");
-template <int KIND>
-static int launch_disk(const RenderArgs& a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh,
-                       const DiskEmitArgs* em, bool adaptive, const LaunchPlan& p) {
-    FrameBatch<1> fb;
-    fb.f[0] = fk;
-    if (adaptive) {  // geo_render_disk_adaptive
-        if (em) return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_emit_kernel<KIND>, fb, d, *em);
-        if (sh) return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_shift_kernel<KIND>, fb, d, *sh);
-        return launch_wave_blocks(a, p, 1, geo_render_disk_adaptive_kernel<KIND>, fb, d);
-    }
-    if (em) return launch_wave_blocks(a, p, 1, geo_render_disk_emit_kernel<KIND>, fb, d, *em);
-    if (sh) return launch_wave_blocks(a, p, 1, geo_render_disk_shift_kernel<KIND>, fb, d, *sh);
-    return launch_wave_blocks(a, p, 1, geo_render_disk_kernel<KIND>, fb, d);
+// f(std::integral_constant<Shade, S>{}) for what a disk render shades, decided
+// here once per call: the emission where it is set (it takes the shift's
+// place), else the shift, else the plain disk.
+template <typename F>
+static int with_shade(bool emit, bool shift, F&& f) {
+    if (emit) return f(std::integral_constant<Shade, Shade::kDiskEmit>{});
+    if (shift) return f(std::integral_constant<Shade, Shade::kDiskShift>{});
+    return f(std::integral_constant<Shade, Shade::kDisk>{});
 }
 
-// The same frame with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel):
-// the band's constants ride as a further argument.  The curved kinds only (a
-// capture orbit needs rs > 0).
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(DiskArgs) + sizeof(DiskVarArgs<kDiskEmit>) +
-                      sizeof(BandArg<true>) <= 4096,
-              "kernel arguments fit 4 KiB");
-template <int KIND>
-static int launch_disk_ring(const RenderArgs& a, const FrameK& fk, const DiskArgs& d, const DiskShiftArgs* sh,
-                            const DiskEmitArgs* em, const geo::BandConsts& band, const LaunchPlan& p) {
-    if constexpr (KIND == geo::kFlat) {
-        return GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
-    } else {
-        FrameBatch<1> fb;
-        fb.f[0] = fk;
-        BandArg<true> bk;
-        bk.k = band;
-        if (em) {
-            DiskVarArgs<kDiskEmit> x;
-            x.em = *em;
-            return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskEmit>, fb, d, x, bk);
-        }
-        if (sh) {
-            DiskVarArgs<kDiskShift> x;
-            x.sh = *sh;
-            return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskShift>, fb, d, x, bk);
-        }
-        return launch_wave_blocks(a, p, 1, geo_render_disk_ring_kernel<KIND, kDiskPlain>, fb, d,
-                                  DiskVarArgs<kDiskPlain>{}, bk);
-    }
+// f(std::true_type{}) or f(std::false_type{}): a render's property as a template argument.
+template <typename F>
+static int with_flag(bool on, F&& f) {
+    return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
-// The batched disk launch (geo_render_disk_batch_kernel), the frames in
-// grid.z.  The one-frame disk render's wave-block grid, not the plain batch's
-// 32 x 8-pixel workgroups: a disk wave holds more registers than a plain one,
-// and its frames are compared with one-frame launches wave for wave.
-static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) <= 4096, "kernel arguments fit 4 KiB");
-template <int KIND>
-static int launch_disk_batch(const RenderArgs& a, const DiskBatchArgs& db, uint32_t nframes, bool shift,
-                             const LaunchPlan& p) {
-    if (shift) return launch_wave_blocks(a, p, nframes, geo_render_disk_batch_kernel<KIND, true>, db);
-    return launch_wave_blocks(a, p, nframes, geo_render_disk_batch_kernel<KIND, false>, db);
+// The emission batch's further kernel argument, or none.
+template <Shade SHADE>
+static ShadeBatchArg<SHADE> shade_batch_arg(const DiskEmitBatchArgs& eb) {
+    if constexpr (SHADE == Shade::kDiskEmit)
+        return eb;
+    else
+        return NoArgs{};
 }
 }
 
@@ -769,7 +729,7 @@ static void fill_args(const geo_ctx* c, const RenderCall& rc, RenderWork& w) {
 #endif
     a.k = w.pk[0];
     // GEO_FLAG_SS4: the sample frame's sizes and rows (twice the call's; the
-    // output's pitch rides in SsArgs).  band_magic stays the call's
+    // output's pitch rides in SsPitch).  band_magic stays the call's
     // band_rows': the SS kernels take the band index on output rows, where
     // band_rows_magic is exact.
     const uint32_t ssf = w.ss ? 2u : 1u;
@@ -930,7 +890,13 @@ static DiskEmitArgs emit_args(const geo_ctx* c, const RenderCall& rc, const Rend
     return em;
 }
 
-// Stage 5, a GEO_FLAG_DISK frame drawn alone.
+// Stage 5, a GEO_FLAG_DISK frame drawn alone (geo_render_disk_frame_kernel):
+// direct, adaptive (geo_render_disk_adaptive) or GEO_FLAG_SS4
+// (geo_render_ss_disk_frame_kernel; colour only: the rules left no per-pixel
+// buffer armed; the disk's constants do not depend on the resolution), or
+// with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel:
+// the band's constants ride as a further argument; the curved kinds only, a
+// capture orbit needs rs > 0).  The rules let no adaptive SS4 frame through.
 static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskArgs d;
     if (!geo::disk_consts(rc.frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out, w.a.k,
@@ -938,79 +904,67 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
         return GEO_EINVAL;
     fill_disk_tex(c, d);
     d.out_hits = w.out_hits;
-    DiskShiftArgs sh;
-    if (c->shift_set) {
-        sh.k = geo::disk_shift_consts(rc.frames[0].central_to_uv, rc.scene->rs, rc.scene->r_obs, c->shift.spin,
-                                      c->shift.exponent, c->shift.gain);
-        sh.out_g = w.out_g;
-    }
-    DiskEmitArgs em;
-    if (w.emit) em = emit_args(c, rc, w);
-    geo::BandConsts band_k;
-    if (w.disk_ring) band_k = geo::band_consts(rc.frames[0], *rc.scene, rc.width, rc.height);
+    FrameBatch<1> fb;
+    fb.f[0] = w.fk[0];
+    BandArg<true> bk;
+    if (w.disk_ring) bk.k = geo::band_consts(rc.frames[0], *rc.scene, rc.width, rc.height);
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        if (w.disk_ring)
-            return launch_disk_ring<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
-                                                           w.emit ? &em : nullptr, band_k, w.p);
-        return launch_disk<decltype(kind)::value>(w.a, w.fk[0], d, c->shift_set ? &sh : nullptr,
-                                                  w.emit ? &em : nullptr, w.adaptive, w.p);
+        return with_shade(w.emit, c->shift_set, [&](auto shade) {
+            constexpr int KIND = decltype(kind)::value;
+            constexpr Shade SHADE = decltype(shade)::value;
+            ShadeFrameArg<SHADE> x;
+            if constexpr (SHADE == Shade::kDiskEmit) x = emit_args(c, rc, w);
+            if constexpr (SHADE == Shade::kDiskShift) {
+                x.k = geo::disk_shift_consts(rc.frames[0].central_to_uv, rc.scene->rs, rc.scene->r_obs, c->shift.spin,
+                                             c->shift.exponent, c->shift.gain);
+                x.out_g = w.out_g;
+            }
+            if (w.disk_ring) {
+                if constexpr (KIND != geo::kFlat)
+                    return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_ring_kernel<KIND, SHADE>, fb, d, x, bk);
+                return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
+            }
+            if (w.ss)
+                return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_disk_frame_kernel<KIND, SHADE>, fb,
+                                          SsDiskArgs<SHADE>{rc.width, d, x});
+            if (w.adaptive)
+                return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_frame_kernel<KIND, SHADE, GEO_MODE_ADAPTIVE>, fb,
+                                          d, x);
+            return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_frame_kernel<KIND, SHADE, GEO_MODE_DIRECT>, fb, d,
+                                      x);
+        });
     });
 }
 
-// Stage 5, a GEO_FLAG_SS4 frame: the plain frame, the disk frame, the shifted
-// disk frame or the emission frame, the disk's constants as launch_disk_frame derives them (they do
-// not depend on the resolution).
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(SsArgs<kSsDiskShift>) <= 4096,
-              "kernel arguments fit 4 KiB");
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<1>) + sizeof(SsEmitArgs) <= 4096, "kernel arguments fit 4 KiB");
-static int launch_ss_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    SsArgs<kSsDiskShift> x;
-    x.out_width = rc.width;
-    if (w.disk) {
-        if (!geo::disk_consts(rc.frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out,
-                              w.a.k, &x.d.k))
-            return GEO_EINVAL;
-        fill_disk_tex(c, x.d);
-        x.d.out_hits = nullptr;
-        if (c->shift_set) {
-            x.sh.k = geo::disk_shift_consts(rc.frames[0].central_to_uv, rc.scene->rs, rc.scene->r_obs, c->shift.spin,
-                                            c->shift.exponent, c->shift.gain);
-            x.sh.out_g = nullptr;
-        }
-    }
-    FrameBatch<1> fb;
-    fb.f[0] = w.fk[0];
+// Stage 5, a GEO_FLAG_SS4 render without a disk (geo_render_ss_sky_kernel): the
+// frame drawn alone, or geo_render_ss_batch's frames in grid.z on the disk
+// batch's geometry.  w.fk holds each frame's camera at 2W x 2H and w.pk its
+// scene constants (fill_frames).
+static int launch_ss_sky(const RenderCall& rc, const RenderWork& w, bool batch) {
+    const SsPitch<true> o{rc.width};
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
         constexpr int KIND = decltype(kind)::value;
-        if (!w.disk) {
-            SsArgs<kSsPlain> xp;
-            xp.out_width = x.out_width;
-            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsPlain>, fb, xp);
+        if (!batch) {
+            FrameBatch<1> fb;
+            fb.f[0] = w.fk[0];
+            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_sky_kernel<KIND, 1>, fb, o);
         }
-        if (w.emit) {
-            SsEmitArgs xe;
-            xe.out_width = x.out_width;
-            xe.d = x.d;
-            xe.em = emit_args(c, rc, w);  // (SS4 is colour only: out_g and out_q are null here)
-            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_emit_kernel<KIND>, fb, xe);
+        FrameBatch<kMaxBatchFrames> fb;
+        std::memset(&fb, 0, sizeof(fb));
+        for (uint32_t i = 0; i < rc.nframes; ++i) {
+            fb.f[i] = w.fk[i];
+            fb.k[i] = w.pk[i];
         }
-        if (!c->shift_set) {
-            SsArgs<kSsDisk> xd;
-            xd.out_width = x.out_width;
-            xd.d = x.d;
-            return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsDisk>, fb, xd);
-        }
-        return launch_wave_blocks(w.a, w.p, 1, geo_render_ss_kernel<KIND, kSsDiskShift>, fb, x);
+        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_sky_kernel<KIND, kMaxBatchFrames>, fb, o);
     });
 }
 
 // A batch's DiskBatchArgs: every frame's constants by the one-frame launch's
-// own functions (geo_render_disk_batch, and geo_render_ss_batch's disk frames,
-// whose w.fk holds the sample frame's camera).  eb (geo_render_emission_batch):
-// the emission's batch-uniform argument, filled too; the frames' sb and ih are
-// then the emission's.
+// own functions (launch_disk_frame; under GEO_FLAG_SS4 w.fk holds the sample
+// frame's camera).  eb (an emission batch): the emission's batch-uniform
+// argument, filled too; the frames' sb and ih are then the emission's.
 static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderWork& w, DiskBatchArgs& db,
-                           DiskEmitBatchArgs* eb = nullptr) {
+                           DiskEmitBatchArgs* eb) {
     std::memset(&db, 0, sizeof(db));
     if (eb) std::memset(eb, 0, sizeof(*eb));
     for (uint32_t i = 0; i < rc.nframes; ++i) {
@@ -1070,160 +1024,77 @@ static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderW
     return GEO_OK;
 }
 
-// Stage 5, geo_render_disk_batch.
-static int launch_disk_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    DiskBatchArgs db;
-    if (const int st = fill_disk_batch(c, rc, w, db)) return st;
-    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        return launch_disk_batch<decltype(kind)::value>(w.a, db, rc.nframes, c->shift_set, w.p);
-    });
-}
-
-// Stage 5, geo_render_ss_batch: launch_ss_frame's three variants with the
-// frames in grid.z (geo_render_ss_batch_kernel), on the disk batch's geometry.
-// w.fk holds each frame's camera at 2W x 2H and w.pk its scene constants
-// (fill_frames); the disk frames' constants are fill_disk_batch's.
-static_assert(sizeof(RenderArgs) + sizeof(FrameBatch<kMaxBatchFrames>) + sizeof(SsBatchOut) <= 4096,
-              "kernel arguments fit 4 KiB");
-static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(SsBatchOut) <= 4096, "kernel arguments fit 4 KiB");
-static int launch_ss_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    SsBatchOut x;
-    x.out_width = rc.width;
-    FrameBatch<kMaxBatchFrames> fb;
-    DiskBatchArgs db;
-    if (w.disk) {
-        if (const int st = fill_disk_batch(c, rc, w, db)) return st;
-    } else {
-        std::memset(&fb, 0, sizeof(fb));
-        for (uint32_t i = 0; i < rc.nframes; ++i) {
-            fb.f[i] = w.fk[i];
-            fb.k[i] = w.pk[i];
-        }
-    }
-    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        constexpr int KIND = decltype(kind)::value;
-        if (!w.disk) return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsPlain>, fb, x);
-        if (!c->shift_set)
-            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsDisk>, db, x);
-        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_batch_kernel<KIND, kSsDiskShift>, db, x);
-    });
-}
-
-// Stage 5, geo_render_emission_batch: launch_disk_batch's and launch_ss_frames'
-// geometry (one wave per workgroup on the 1-D wave-block grid, the frames in
-// grid.z) with the emission kernels; with GEO_FLAG_SS4, w.fk holds each
-// frame's camera at 2W x 2H and the grid is the sample frame's.
-static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(DiskEmitBatchArgs) + sizeof(SsBatchOut) <= 4096,
-              "kernel arguments fit 4 KiB");
-static int launch_emit_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    DiskBatchArgs db;
-    DiskEmitBatchArgs eb;
-    if (const int st = fill_disk_batch(c, rc, w, db, &eb)) return st;
-    SsBatchOut x;
-    x.out_width = rc.width;
-    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        constexpr int KIND = decltype(kind)::value;
-        if (w.ss) return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_emit_batch_kernel<KIND>, db, eb, x);
-        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_emit_batch_kernel<KIND>, db, eb);
-    });
-}
-
-// Stage 5, geo_render_disk_ring_batch with a capture orbit to draw: the disk
-// batch's, the SS batch's disk frames' and the emission batch's launch with the
-// ring kernels.  Each frame's band constants come from the one-frame launch's
-// geo::band_consts (launch_disk_frame), at the sample frame's size under
-// GEO_FLAG_SS4, and reach the kernel through the device table of the call's
-// render-stream slot (geo_ctx::band_table), written on the call's stream by
-// geo_band_table_kernel just before the render launch: no host copy, no wait.
-static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(RingBatchArgs<kDiskEmit>) + sizeof(SsBatchOut) <=
-                  4096,
-              "kernel arguments fit 4 KiB");
-static int launch_ring_frames(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
+// Stage 5, a batch of GEO_FLAG_DISK frames (geo_render_disk_batch,
+// geo_render_ss_batch's disk frames, geo_render_emission_batch,
+// geo_render_disk_adaptive_batch, and geo_render_disk_ring_batch with or without
+// a capture orbit to draw): geo_render_disk_batch_kernel with the frames in
+// grid.z, on the one-frame disk render's wave-block grid, not the plain batch's
+// 32 x 8-pixel workgroups: a disk wave holds more registers than a plain one,
+// and its frames are compared with one-frame launches wave for wave.
+// With a capture orbit, the ring kernels: each frame's band constants come from
+// the one-frame launch's geo::band_consts (launch_disk_frame), at the sample
+// frame's size under GEO_FLAG_SS4, and reach the kernel through the device table
+// of the call's render-stream slot (geo_ctx::band_table), written on the call's
+// stream by geo_band_table_kernel just before the render launch: no host copy,
+// no wait.  The rules let no adaptive ring batch through.
+static int launch_disk_frames(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskBatchArgs db;
     DiskEmitBatchArgs eb;
     if (const int st = fill_disk_batch(c, rc, w, db, w.emit ? &eb : nullptr)) return st;
-    BandTable bt;
-    std::memset(&bt, 0, sizeof(bt));
-    const uint32_t ssf = w.ss ? 2u : 1u;
-    for (uint32_t i = 0; i < rc.nframes; ++i)
-        bt.k[i] = geo::band_consts(rc.frames[i], traits(rc.entry).scene_per_frame ? rc.scene[i] : *rc.scene,
-                                   ssf * rc.width, ssf * rc.height);
-    void*& table = c->band_table[w.slot];
-    if (!table && hipMalloc(&table, sizeof(BandTable)) != hipSuccess) {
-        table = nullptr;
-        return GEO_ENOMEM;
+    const geo::BandConsts* bands = nullptr;
+    if (w.disk_ring) {
+        BandTable bt;
+        std::memset(&bt, 0, sizeof(bt));
+        const uint32_t ssf = w.ss ? 2u : 1u;
+        for (uint32_t i = 0; i < rc.nframes; ++i)
+            bt.k[i] = geo::band_consts(rc.frames[i], traits(rc.entry).scene_per_frame ? rc.scene[i] : *rc.scene,
+                                       ssf * rc.width, ssf * rc.height);
+        void*& table = c->band_table[w.slot];
+        if (!table && hipMalloc(&table, sizeof(BandTable)) != hipSuccess) {
+            table = nullptr;
+            return GEO_ENOMEM;
+        }
+        bands = static_cast<const geo::BandConsts*>(table);
+        hipLaunchKernelGGL(geo_band_table_kernel, dim3(rc.nframes), dim3(64), 0, w.p.s, bt,
+                           static_cast<geo::BandConsts*>(table));
+        if (hipGetLastError() != hipSuccess) return GEO_EHIP;
     }
-    geo::BandConsts* const bands = static_cast<geo::BandConsts*>(table);
-    hipLaunchKernelGGL(geo_band_table_kernel, dim3(rc.nframes), dim3(64), 0, w.p.s, bt, bands);
-    if (hipGetLastError() != hipSuccess) return GEO_EHIP;
-    SsBatchOut o;
-    o.out_width = rc.width;
     return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        constexpr int KIND = decltype(kind)::value;
-        if constexpr (KIND == geo::kFlat) {
-            return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
-        } else {
-            const auto run = [&](auto var, const auto& x) {
-                constexpr int VAR = decltype(var)::value;
-                if (w.ss)
-                    return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_ring_batch_kernel<KIND, VAR>, db, x,
-                                              o);
-                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_ring_batch_kernel<KIND, VAR>, db, x);
-            };
-            if (w.emit) {
-                RingBatchArgs<kDiskEmit> x;
-                x.bands = bands;
-                x.eb = eb;
-                return run(std::integral_constant<int, kDiskEmit>{}, x);
-            }
-            if (c->shift_set) return run(std::integral_constant<int, kDiskShift>{}, RingBatchArgs<kDiskShift>{bands});
-            return run(std::integral_constant<int, kDiskPlain>{}, RingBatchArgs<kDiskPlain>{bands});
-        }
-    });
-}
-
-// Stage 5, geo_render_disk_adaptive_batch: launch_emit_frames' and
-// launch_ring_frames' form with the adaptive disk kernels.  The frames'
-// constants are fill_disk_batch's, the one-frame adaptive launch's own
-// (launch_disk_frame: geo::disk_ray_adaptive reads the same geo::DiskConsts);
-// with GEO_FLAG_SS4, w.fk holds each frame's camera at 2W x 2H and the grid is
-// the sample frame's.
-static_assert(sizeof(RenderArgs) + sizeof(DiskBatchArgs) + sizeof(DiskEmitBatchArgs) + sizeof(SsBatchOut) <= 4096,
-              "kernel arguments fit 4 KiB");
-static int launch_adaptive_frames(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
-    DiskBatchArgs db;
-    DiskEmitBatchArgs eb;
-    if (const int st = fill_disk_batch(c, rc, w, db, w.emit ? &eb : nullptr)) return st;
-    SsBatchOut x;
-    x.out_width = rc.width;
-    return with_kind(geo::geodesic_kind(w.a.k), [&](auto kind) {
-        constexpr int KIND = decltype(kind)::value;
-        if (w.emit) {
-            if (w.ss)
-                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_emit_batch_kernel<KIND>, db, eb,
-                                          x);
-            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_emit_batch_kernel<KIND>, db, eb);
-        }
-        if (c->shift_set) {
-            if (w.ss)
-                return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_batch_kernel<KIND, true>, db, x);
-            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_batch_kernel<KIND, true>, db);
-        }
-        if (w.ss)
-            return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_ss_adaptive_batch_kernel<KIND, false>, db, x);
-        return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_adaptive_batch_kernel<KIND, false>, db);
+        return with_shade(w.emit, c->shift_set, [&](auto shade) {
+            constexpr int KIND = decltype(kind)::value;
+            constexpr Shade SHADE = decltype(shade)::value;
+            const ShadeBatchArg<SHADE> x = shade_batch_arg<SHADE>(eb);
+            return with_flag(w.ss, [&](auto ss) {
+                constexpr bool SS = decltype(ss)::value;
+                SsPitch<SS> o;
+                if constexpr (SS) o.out_width = rc.width;
+                if (w.disk_ring) {
+                    if constexpr (KIND != geo::kFlat)
+                        return launch_wave_blocks(w.a, w.p, rc.nframes,
+                                                  geo_render_disk_ring_batch_kernel<KIND, SHADE, SS>, db, bands, x, o);
+                    return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
+                }
+                return with_flag(w.adaptive, [&](auto adaptive) {
+                    constexpr int MODE = decltype(adaptive)::value ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT;
+                    return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_batch_kernel<KIND, SHADE, SS, MODE>,
+                                              db, x, o);
+                });
+            });
+        });
     });
 }
 
 // Stage 5: the launch.
 static int launch_render(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     switch (choose_launcher(rc, w)) {
-        case Launcher::kAdaptiveFrames: return launch_adaptive_frames(c, rc, w);
-        case Launcher::kRingFrames: return launch_ring_frames(c, rc, w);
-        case Launcher::kEmitFrames: return launch_emit_frames(c, rc, w);
-        case Launcher::kSsFrames: return launch_ss_frames(c, rc, w);
+        // (what the batched disk launchers differ in, the launch reads from w:
+        // the shade, SS4, the integrator and whether there is a band to draw)
+        case Launcher::kAdaptiveFrames:
+        case Launcher::kRingFrames:
+        case Launcher::kEmitFrames:
         case Launcher::kDiskFrames: return launch_disk_frames(c, rc, w);
-        case Launcher::kSsFrame: return launch_ss_frame(c, rc, w);
+        case Launcher::kSsFrames: return w.disk ? launch_disk_frames(c, rc, w) : launch_ss_sky(rc, w, true);
+        case Launcher::kSsFrame: return w.disk ? launch_disk_frame(c, rc, w) : launch_ss_sky(rc, w, false);
         case Launcher::kDiskFrame: return launch_disk_frame(c, rc, w);
         case Launcher::kFan: return launch_fan(c, rc, w);
         case Launcher::kFrames: break;

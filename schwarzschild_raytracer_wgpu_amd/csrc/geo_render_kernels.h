@@ -689,9 +689,34 @@ struct DiskEmitArgs {
     float* out_q;          // optional: 3 x q per pixel
 };
 
+// What a wave-block kernel shades: the sky alone, or the disk plain, shifted or
+// with its emission.  The host decides it once per call (geo_render.hip).
+enum class Shade { kSky, kDisk, kDiskShift, kDiskEmit };
+// A kernel argument that an instantiation does not have: the shade's own
+// (ShadeFrameArg, ShadeBatchArg below) of an unshaded render, the output pitch
+// (SsPitch) of a one-sample one.
+struct NoArgs {};
+// They fit the 4 KiB argument segment (each padded to 8 bytes at most).
+template <typename... A>
+constexpr bool kKernargsFit = (((sizeof(A) + 7u) / 8u * 8u) + ...) <= 4096u;
+template <Shade SHADE>
+using ShadeFrameArg = std::conditional_t<SHADE == Shade::kDiskEmit, DiskEmitArgs,
+                                         std::conditional_t<SHADE == Shade::kDiskShift, DiskShiftArgs, NoArgs>>;
+// GEO_FLAG_SS4: the output's pitch in pixels (RenderArgs::width is then the
+// sample frame's, twice it).
+template <bool SS>
+struct SsPitch {
+    __device__ __forceinline__ uint32_t width() const { return 0u; }
+};
+template <>
+struct SsPitch<true> {
+    uint32_t out_width;
+    __device__ __forceinline__ uint32_t width() const { return out_width; }
+};
+
 
 // ---- geo_set_disk_ring_f64: the disk's capture band in f64 ----------------
-// The three one-frame disk renders (VAR: unshaded, shifted, emission)
+// The three one-frame disk renders (SHADE: unshaded, shifted, emission)
 // with the band's lanes (geo::in_band on the f32 ray, GEO_FLAG_RING_F64's
 // test) taken through the f64 path of geo_band.h, probes included
 // (geo::disk_hits_band).  Kernels with their own body on the same launch
@@ -704,23 +729,12 @@ struct DiskEmitArgs {
 // band lane's steps count twice in its tile's cost.  Both kinds of lane hand
 // their crossings on as geo::DiskHits, and one shading follows.  rs > 0 and
 // r_obs > rs (a capture orbit): the curved kinds only.
-constexpr int kDiskPlain = 0, kDiskShift = 1, kDiskEmit = 2;
-template <int VAR>
-struct DiskVarArgs {};
-template <>
-struct DiskVarArgs<kDiskShift> {
-    DiskShiftArgs sh;
-};
-template <>
-struct DiskVarArgs<kDiskEmit> {
-    DiskEmitArgs em;
-};
-
-template <int KIND, int VAR>
+template <int KIND, Shade SHADE>
 __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                  const DiskArgs d, const DiskVarArgs<VAR> x,
+                                                                  const DiskArgs d, const ShadeFrameArg<SHADE> x,
                                                                   const BandArg<true> bk) {
-    static_assert(KIND != geo::kFlat, "no capture orbit without a black hole");
+    static_assert(KIND != geo::kFlat && SHADE != Shade::kSky, "no capture orbit without a black hole; a disk render");
+    static_assert(kKernargsFit<RenderArgs, FrameBatch<1>, DiskArgs, ShadeFrameArg<SHADE>, BandArg<true>>);
     const FrameK& f = fb.f[0];
     const uint32_t L = blockIdx.x;
     const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
@@ -750,7 +764,7 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
     bool f64_lane = false;
     if (px < a.width && ly < a.nrows && py < a.height) {
         float c2x, c2y, c2z, g_obs = 1.0f;
-        if constexpr (VAR == kDiskPlain)
+        if constexpr (SHADE == Shade::kDisk)
             geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px,
                                    py, &c2x, &c2y, &c2z);
         else
@@ -797,8 +811,8 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
             return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
         };
         float* const hits = d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
-        if constexpr (VAR == kDiskEmit) {
-            const DiskEmitArgs& em = x.em;
+        if constexpr (SHADE == Shade::kDiskEmit) {
+            const DiskEmitArgs& em = x;
             const auto rfetch = [ramp = em.ramp](uint32_t i) { return ramp[i]; };
             geo::DiskShiftRay sr;
             geo::disk_shift_ray(d.k, em.k.s, dr, ct, g_obs, &sr);
@@ -806,8 +820,8 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
                                                  geo::disk_colour_emit(d.k, a.k, em.k, sr, dsample, rfetch), hits,
                                                  em.out_g ? em.out_g + o * geo::kDiskMaxCrossings : nullptr,
                                                  em.out_q ? em.out_q + o * geo::kDiskMaxCrossings : nullptr);
-        } else if constexpr (VAR == kDiskShift) {
-            const DiskShiftArgs& sh = x.sh;
+        } else if constexpr (SHADE == Shade::kDiskShift) {
+            const DiskShiftArgs& sh = x;
             geo::DiskShiftRay sr;
             geo::disk_shift_ray(d.k, sh.k, dr, ct, g_obs, &sr);
             a.out_rgba[o] = geo::disk_shade_hits(d.k, dr, h, base, geo::disk_colour_shift(a.k, sh.k, sr, dsample),
@@ -881,24 +895,7 @@ struct DiskBatchArgs {
 // size), so a lane traces and shades pixel (px, py) of the 2W x 2H render
 // exactly as its one-sample sibling does, keeps the colour in a register, and
 // the wave's 16 x 4 samples are resolved to 8 x 2 output pixels across its
-// lanes.  VAR: the plain frame, the disk frame, the shifted disk frame, each
-// with its own further argument.
-constexpr int kSsPlain = 0, kSsDisk = 1, kSsDiskShift = 2;
-template <int VAR>
-struct SsArgs {
-    uint32_t out_width;  // the output's pitch in pixels (RenderArgs::width is the sample frame's, twice it)
-};
-template <>
-struct SsArgs<kSsDisk> {
-    uint32_t out_width;
-    DiskArgs d;
-};
-template <>
-struct SsArgs<kSsDiskShift> {
-    uint32_t out_width;
-    DiskArgs d;
-    DiskShiftArgs sh;
-};
+// lanes.  The output's pitch rides in SsPitch<true>.
 
 // lane_xor1 / lane_xor16 on integers: a sample's x and y partners in its
 // output pixel's 2 x 2 quad.
@@ -927,35 +924,17 @@ __device__ __forceinline__ uint32_t ss_resolve(uint32_t c) {
     return rb | (ga << 8);
 }
 
-// The supersampled emission frame (geo_set_disk_emission with GEO_FLAG_SS4).
-struct SsEmitArgs {
-    uint32_t out_width;
-    DiskArgs d;
-    DiskEmitArgs em;
-};
-
 // ---- geo_render_ss_batch: up to kMaxBatchFrames GEO_FLAG_SS4 frames in one launch --
-// geo_render_ss_kernel with the frame in blockIdx.z, on the disk batch's
+// The one-frame SS4 renders with the frame in blockIdx.z, on the disk batch's
 // geometry: one wave per workgroup on the 1-D wave-block grid, grid.z frames.
 // Frame z's constants come from the batched kernels' own argument structs,
-// indexed by z (uniform: scalar loads): the plain variant reads
-// FrameBatch<kMaxBatchFrames> (f[z], k[z]), the disk variants DiskBatchArgs
+// indexed by z (uniform: scalar loads): the sky-only render reads
+// FrameBatch<kMaxBatchFrames> (f[z], k[z]), the disk renders DiskBatchArgs
 // (DiskFrameK, assembled into geo::DiskConsts and geo::DiskShift by
 // DiskBatchFrame below).  The host fills both with the one-frame
 // SS launch's functions at the sample frame's size, so a batch frame is its
-// one-frame render bit for bit.  The output's pitch rides in SsBatchOut; frame
-// z's output starts a.out_frame_px output pixels after frame z - 1's.
-struct SsBatchOut {
-    uint32_t out_width;  // the output's pitch in pixels (RenderArgs::width is the sample frame's, twice it)
-};
-template <int VAR>
-struct SsBatchFrames {
-    using type = DiskBatchArgs;
-};
-template <>
-struct SsBatchFrames<kSsPlain> {
-    using type = FrameBatch<kMaxBatchFrames>;
-};
+// one-frame render bit for bit.  Frame z's output starts a.out_frame_px output
+// pixels after frame z - 1's.
 
 // ---- geo_render_emission_batch: up to kMaxBatchFrames emission frames in one launch --
 // The shaded disk batch and the SS batch's disk frames with
@@ -966,21 +945,28 @@ struct SsBatchFrames<kSsPlain> {
 // with the emission's spin; the batch-uniform rest and the ramp ride in one
 // further argument.  Everything read here per frame or per batch is
 // wave-uniform (scalar loads); the ramp's two entries are loaded inside the hit
-// arm only, as in geo_render_disk_emit_kernel.
+// arm only, as in the one-frame emission render.
 struct DiskEmitBatchArgs {
     float inv_fmax, ka, kb, n1, exposure;  // geo::DiskEmission, batch-uniform
     uint32_t profile, n2;
     const uint32_t* ramp;  // n2 + 2 RGBA8 entries
 };
+template <Shade SHADE>
+using ShadeBatchArg = std::conditional_t<SHADE == Shade::kDiskEmit, DiskEmitBatchArgs, NoArgs>;
 
 // ---- the one body of the disk and SS4 kernels on the wave-block grid ------
-// Every kernel below (all of this file's wave-block kernels but
-// geo_render_kernel and the ring kernels) is a wrapper that names its frame
-// source and calls wave_block_body, which holds what they share: the tile
-// mapping, the camera ray, geo::disk_ray and geo::geodesic_angle_disk, the sky
-// sample, the disk texture quad, the shading call, the SS4 resolve, and the
-// step-slot and tile-cost epilogue.  It varies along five properties of the
-// render, not of the caller:
+// The four kernels below (all of this file's wave-block kernels but
+// geo_render_kernel and the ring kernels) are one wrapper per argument layout:
+// the sky-only SS4 render, one disk frame, that frame with SS4, a disk batch.
+// Each names its frame source and calls wave_block_body, which holds what they
+// share: the tile mapping, the camera ray, geo::disk_ray and
+// geo::geodesic_angle_disk, the sky sample, the disk texture quad, the shading
+// call, the SS4 resolve, and the step-slot and tile-cost epilogue.  (The ring
+// bodies spell the mapping and the epilogue again: as shared __forceinline__
+// helpers they changed the instruction selection of every kernel here, a
+// handful of scalar instructions each, and are not kept;
+// profiles/wave_block_wrappers_isa.txt.)  It varies along five properties of
+// the render, not of the caller:
 //   SHADE  what is shaded: the sky alone (pixel_lambda), or the disk plain,
 //          shifted or with its emission (geo::disk_shade, _shift, _emit)
 //   SS     one sample per pixel, or GEO_FLAG_SS4: a lane per sample, the band
@@ -1002,11 +988,13 @@ struct DiskEmitBatchArgs {
 //          where its output starts and whether it records tile costs, one
 //          struct per argument layout (SkyFrame<1>, SkyFrame<kMaxBatchFrames>,
 //          DiskFrame, DiskBatchFrame)
-// A new variant is a new value of a property and a wrapper, not a copy of the
-// body.  One body on the CPU path too (run_rows_disk, cpu_render.cpp), which
-// every wrapper is tested against bit for bit.
-enum class Shade { kSky, kDisk, kDiskShift, kDiskEmit };
-struct NoArgs {};
+// A new variant is a new value of a property, which the wrappers take as a
+// template argument and the host's launchers pass on (geo_render.hip): not a
+// wrapper, an argument struct or a launcher of its own, and not a copy of the
+// body.  An argument that an instantiation lacks is NoArgs.  One body on the
+// CPU path too (run_rows_disk, cpu_render.cpp), which every instantiation is
+// tested against bit for bit (tests/test_gpu_wave_block_matrix.py: one cell
+// each).
 
 // FrameBatch<NF> and the scene constants of frame_consts: the sky-only renders
 // (and, as DiskFrame's base, the one-frame disk renders).
@@ -1247,138 +1235,54 @@ __device__ __forceinline__ void wave_block_body(const RenderArgs& a, const SRC& 
     }
 }
 
-// The one-frame disk renders: plain, shifted (geo_set_disk_shift), emission
-// (geo_set_disk_emission).
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                             const DiskArgs d) {
-    wave_block_body<KIND, Shade::kDisk, false, true>(a, DiskFrame<NoArgs>{{a, fb, 0u}, d, NoArgs{}}, 0u);
+// The sky-only GEO_FLAG_SS4 render: one frame (NF = 1), or geo_render_ss_batch's
+// frames (NF = kMaxBatchFrames, the frame in blockIdx.z).
+template <int KIND, uint32_t NF>
+__global__ __launch_bounds__(64) void geo_render_ss_sky_kernel(const RenderArgs a, const FrameBatch<NF> fb,
+                                                               const SsPitch<true> o) {
+    static_assert(kKernargsFit<RenderArgs, FrameBatch<NF>, SsPitch<true>>);
+    wave_block_body<KIND, Shade::kSky, true, false>(a, SkyFrame<NF>{a, fb, NF > 1 ? blockIdx.z : 0u}, o.width());
 }
 
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_shift_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                   const DiskArgs d, const DiskShiftArgs sh) {
-    wave_block_body<KIND, Shade::kDiskShift, false, true>(a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, d, sh}, 0u);
+// One disk frame, one sample per pixel, with the side outputs: plain, shifted
+// (geo_set_disk_shift) or with its emission (geo_set_disk_emission), x being
+// the shade's own argument; direct or adaptive (geo_render_disk_adaptive).
+template <int KIND, Shade SHADE, int MODE>
+__global__ __launch_bounds__(64) void geo_render_disk_frame_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                   const DiskArgs d, const ShadeFrameArg<SHADE> x) {
+    static_assert(kKernargsFit<RenderArgs, FrameBatch<1>, DiskArgs, ShadeFrameArg<SHADE>>);
+    wave_block_body<KIND, SHADE, false, true, MODE>(a, DiskFrame<ShadeFrameArg<SHADE>>{{a, fb, 0u}, d, x}, 0u);
 }
 
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                  const DiskArgs d, const DiskEmitArgs em) {
-    wave_block_body<KIND, Shade::kDiskEmit, false, true>(a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, d, em}, 0u);
+// The same frame with GEO_FLAG_SS4, colour only.  Its arguments stay one
+// struct, the output's pitch first: a small argument of its own (the pitch, a
+// shift's 24 bytes) is loaded at the kernel's entry, a member of a large one
+// where it is used, and as three arguments these nine kernels came out with
+// their scalar loads moved and their registers renumbered
+// (profiles/wave_block_wrappers_isa.txt).
+template <Shade SHADE>
+struct SsDiskArgs {
+    uint32_t out_width;  // SsPitch<true>'s
+    DiskArgs d;
+    ShadeFrameArg<SHADE> x;
+};
+template <int KIND, Shade SHADE>
+__global__ __launch_bounds__(64) void geo_render_ss_disk_frame_kernel(const RenderArgs a, const FrameBatch<1> fb,
+                                                                      const SsDiskArgs<SHADE> s) {
+    static_assert(kKernargsFit<RenderArgs, FrameBatch<1>, SsDiskArgs<SHADE>>);
+    wave_block_body<KIND, SHADE, true, false>(a, DiskFrame<ShadeFrameArg<SHADE>>{{a, fb, 0u}, s.d, s.x}, s.out_width);
 }
 
-// geo_render_disk_adaptive: the same three renders with the adaptive
-// integrator (the argument layouts are the direct kernels').
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                      const DiskArgs d) {
-    wave_block_body<KIND, Shade::kDisk, false, true, GEO_MODE_ADAPTIVE>(
-        a, DiskFrame<NoArgs>{{a, fb, 0u}, d, NoArgs{}}, 0u);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_shift_kernel(const RenderArgs a,
-                                                                            const FrameBatch<1> fb, const DiskArgs d,
-                                                                            const DiskShiftArgs sh) {
-    wave_block_body<KIND, Shade::kDiskShift, false, true, GEO_MODE_ADAPTIVE>(
-        a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, d, sh}, 0u);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_emit_kernel(const RenderArgs a,
-                                                                           const FrameBatch<1> fb, const DiskArgs d,
-                                                                           const DiskEmitArgs em) {
-    wave_block_body<KIND, Shade::kDiskEmit, false, true, GEO_MODE_ADAPTIVE>(
-        a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, d, em}, 0u);
-}
-
-// geo_render_disk_batch.  SHIFT: the shaded batch (geo_set_disk_shift).
-template <int KIND, bool SHIFT>
-__global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderArgs a, const DiskBatchArgs db) {
-    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, false, false>(
-        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, 0u);
-}
-
-// GEO_FLAG_SS4, one frame.
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) void geo_render_ss_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                           const SsArgs<VAR> x) {
-    if constexpr (VAR == kSsPlain)
-        wave_block_body<KIND, Shade::kSky, true, false>(a, SkyFrame<1>{a, fb, 0u}, x.out_width);
-    else if constexpr (VAR == kSsDisk)
-        wave_block_body<KIND, Shade::kDisk, true, false>(a, DiskFrame<NoArgs>{{a, fb, 0u}, x.d, NoArgs{}}, x.out_width);
-    else
-        wave_block_body<KIND, Shade::kDiskShift, true, false>(a, DiskFrame<DiskShiftArgs>{{a, fb, 0u}, x.d, x.sh},
-                                                              x.out_width);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_ss_emit_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                const SsEmitArgs x) {
-    wave_block_body<KIND, Shade::kDiskEmit, true, false>(a, DiskFrame<DiskEmitArgs>{{a, fb, 0u}, x.d, x.em},
-                                                         x.out_width);
-}
-
-// geo_render_ss_batch.
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) void geo_render_ss_batch_kernel(const RenderArgs a,
-                                                                 const typename SsBatchFrames<VAR>::type fb,
-                                                                 const SsBatchOut x) {
-    if constexpr (VAR == kSsPlain)
-        wave_block_body<KIND, Shade::kSky, true, false>(a, SkyFrame<kMaxBatchFrames>{a, fb, blockIdx.z}, x.out_width);
-    else
-        wave_block_body<KIND, VAR == kSsDiskShift ? Shade::kDiskShift : Shade::kDisk, true, false>(
-            a, DiskBatchFrame<NoArgs>{a, fb, NoArgs{}, blockIdx.z}, x.out_width);
-}
-
-// geo_render_emission_batch, and the same with GEO_FLAG_SS4.
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                        const DiskEmitBatchArgs eb) {
-    wave_block_body<KIND, Shade::kDiskEmit, false, false>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z},
-                                                          0u);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_ss_emit_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                      const DiskEmitBatchArgs eb,
-                                                                      const SsBatchOut x) {
-    wave_block_body<KIND, Shade::kDiskEmit, true, false>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z},
-                                                         x.out_width);
-}
-
-// geo_render_disk_adaptive_batch: the disk batch's, the SS batch's disk frames'
-// and the emission batch's kernels with the adaptive integrator (the argument
-// layouts are theirs).
-template <int KIND, bool SHIFT>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_batch_kernel(const RenderArgs a,
-                                                                            const DiskBatchArgs db) {
-    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, false, false, GEO_MODE_ADAPTIVE>(
-        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, 0u);
-}
-
-template <int KIND, bool SHIFT>
-__global__ __launch_bounds__(64) void geo_render_ss_adaptive_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                          const SsBatchOut x) {
-    wave_block_body<KIND, SHIFT ? Shade::kDiskShift : Shade::kDisk, true, false, GEO_MODE_ADAPTIVE>(
-        a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, x.out_width);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_emit_batch_kernel(const RenderArgs a,
-                                                                                 const DiskBatchArgs db,
-                                                                                 const DiskEmitBatchArgs eb) {
-    wave_block_body<KIND, Shade::kDiskEmit, false, false, GEO_MODE_ADAPTIVE>(
-        a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z}, 0u);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(64) void geo_render_ss_adaptive_emit_batch_kernel(const RenderArgs a,
-                                                                               const DiskBatchArgs db,
-                                                                               const DiskEmitBatchArgs eb,
-                                                                               const SsBatchOut x) {
-    wave_block_body<KIND, Shade::kDiskEmit, true, false, GEO_MODE_ADAPTIVE>(
-        a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, eb, blockIdx.z}, x.out_width);
+// A disk batch (geo_render_disk_batch, geo_render_ss_batch's disk frames,
+// geo_render_emission_batch, geo_render_disk_adaptive_batch): the frame in
+// blockIdx.z, colour only; eb is the emission's batch-uniform argument.
+template <int KIND, Shade SHADE, bool SS, int MODE>
+__global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
+                                                                   const ShadeBatchArg<SHADE> eb,
+                                                                   const SsPitch<SS> o) {
+    static_assert(kKernargsFit<RenderArgs, DiskBatchArgs, ShadeBatchArg<SHADE>, SsPitch<SS>>);
+    wave_block_body<KIND, SHADE, SS, false, MODE>(a, DiskBatchFrame<ShadeBatchArg<SHADE>>{a, db, eb, blockIdx.z},
+                                                  o.width());
 }
 
 // ---- the one body of the batched disk kernels with the f64 band -----------
@@ -1387,7 +1291,7 @@ __global__ __launch_bounds__(64) void geo_render_ss_adaptive_emit_batch_kernel(c
 // geo::disk_hits_band in a cold arm behind one ballot, then one
 // geo::disk_shade_hits) with wave_block_body's frame source, colour-only
 // output and SS4 resolve.  It varies along
-//   VAR    the shading: kDiskPlain, kDiskShift, kDiskEmit
+//   SHADE  the shading: Shade::kDisk, kDiskShift, kDiskEmit
 //   SS     GEO_FLAG_SS4, as in wave_block_body (the band's constants are then
 //          the sample frame's, and px, py the sample's)
 //   SRC    the frame source (DiskBatchFrame)
@@ -1398,10 +1302,10 @@ __global__ __launch_bounds__(64) void geo_render_ss_adaptive_emit_batch_kernel(c
 // (with DiskFrame as its source and its side outputs as a property) its shaded
 // instantiations came out with 81 VGPRs instead of 80, five waves per SIMD
 // instead of six.
-template <int KIND, int VAR, bool SS, typename SRC>
+template <int KIND, Shade SHADE, bool SS, typename SRC>
 __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& src, const uint2* band_words,
                                                uint32_t out_width) {
-    static_assert(KIND != geo::kFlat, "no capture orbit without a black hole");
+    static_assert(KIND != geo::kFlat && SHADE != Shade::kSky, "no capture orbit without a black hole; a disk render");
     const uint32_t L = blockIdx.x;
     const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
     const uint32_t wave = (L >> 3) & 3u;
@@ -1431,7 +1335,7 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
     bool f64_lane = false;
     if (in_frame) {
         float c2x, c2y, c2z, g_obs = 1.0f;
-        if constexpr (VAR == kDiskPlain)
+        if constexpr (SHADE == Shade::kDisk)
             geo::pixel_central_dir(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y, &c2z);
         else
             geo::pixel_central_dir_g(src.cam(), src.movement_to_central(), src.psi(), src.kt(), px, py, &c2x, &c2y,
@@ -1479,14 +1383,14 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
             return geo::sample_sky_quad_f(dquad, t.tex_w256, t.tex_h256, Ud, Vd);
         };
         float* const none = nullptr;  // a batch draws colour only: no hits, g or q
-        if constexpr (VAR == kDiskEmit) {
+        if constexpr (SHADE == Shade::kDiskEmit) {
             const auto rfetch = [ramp = src.ramp()](uint32_t i) { return ramp[i]; };
             const auto& ek = src.emission();
             geo::DiskShiftRay sr;
             geo::disk_shift_ray(dk, ek.s, dr, ct, g_obs, &sr);
             colour = geo::disk_shade_hits(dk, dr, h, base, geo::disk_colour_emit(dk, k, ek, sr, dsample, rfetch), none,
                                           none, none);
-        } else if constexpr (VAR == kDiskShift) {
+        } else if constexpr (SHADE == Shade::kDiskShift) {
             const auto& sk = src.shift();
             geo::DiskShiftRay sr;
             geo::disk_shift_ray(dk, sk, dr, ct, g_obs, &sr);
@@ -1518,7 +1422,7 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
 }
 
 // ---- geo_render_disk_ring_batch: up to kMaxBatchFrames ring frames in one launch --
-// The disk batch, the SS batch's disk frames and the emission batch (VAR) with
+// The disk batch, the SS batch's disk frames and the emission batch (SHADE) with
 // the band's lanes in f64: disk_ring_body on DiskBatchFrame, the frame in
 // blockIdx.z.  The argument segment has no room for eight frames'
 // geo::BandConsts (8 x 344 bytes beside DiskBatchArgs' 3312), nor for the
@@ -1538,45 +1442,30 @@ __global__ __launch_bounds__(64) void geo_band_table_kernel(const BandTable t, g
             reinterpret_cast<const uint2*>(&t.k[blockIdx.x])[threadIdx.x];
 }
 
-template <int VAR>
-struct RingBatchArgs {
-    const geo::BandConsts* bands;  // the table: frame z's constants at bands[z]
-};
-template <>
-struct RingBatchArgs<kDiskEmit> {
-    const geo::BandConsts* bands;
-    DiskEmitBatchArgs eb;
-};
-
-template <int KIND, int VAR, bool SS>
+// bands: the table, frame z's constants at bands[z]; eb: the emission's
+// batch-uniform argument.
+template <int KIND, Shade SHADE, bool SS>
 __device__ __forceinline__ void disk_ring_batch(const RenderArgs& a, const DiskBatchArgs& db,
-                                                const RingBatchArgs<VAR>& x, uint32_t out_width) {
-    const uint2* const words = reinterpret_cast<const uint2*>(x.bands + blockIdx.z);
-    if constexpr (VAR == kDiskEmit)
-        disk_ring_body<KIND, VAR, SS>(a, DiskBatchFrame<DiskEmitBatchArgs>{a, db, x.eb, blockIdx.z}, words,
-                                             out_width);
-    else
-        disk_ring_body<KIND, VAR, SS>(a, DiskBatchFrame<NoArgs>{a, db, NoArgs{}, blockIdx.z}, words, out_width);
+                                                const geo::BandConsts* bands, const ShadeBatchArg<SHADE>& eb,
+                                                uint32_t out_width) {
+    static_assert(kKernargsFit<RenderArgs, DiskBatchArgs, const geo::BandConsts*, ShadeBatchArg<SHADE>, SsPitch<SS>>);
+    disk_ring_body<KIND, SHADE, SS>(a, DiskBatchFrame<ShadeBatchArg<SHADE>>{a, db, eb, blockIdx.z},
+                                    reinterpret_cast<const uint2*>(bands + blockIdx.z), out_width);
 }
 
 // (amdgpu_waves_per_eu: the one-frame ring kernels' six waves per SIMD as the
-// allocator's target.  Left to itself it gave the emission instantiations 81
-// VGPRs, one over the class, for the lanes of an SGPR it moved to a VGPR: a
-// batch reads its frame's constants through db.f[z] and holds more scalars
-// (106) than the one-frame kernel (100).  With the target they take 80, the
-// others are unchanged, and none uses scratch; profiles/disk_ring_batch_isa.txt.)
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void geo_render_disk_ring_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                        const RingBatchArgs<VAR> x) {
-    disk_ring_batch<KIND, VAR, false>(a, db, x, 0u);
-}
-
-// The same with GEO_FLAG_SS4: a lane per sample of the 2W x 2H ring render.
-template <int KIND, int VAR>
-__global__ __launch_bounds__(64) void geo_render_ss_ring_batch_kernel(const RenderArgs a, const DiskBatchArgs db,
-                                                                      const RingBatchArgs<VAR> x,
-                                                                      const SsBatchOut o) {
-    disk_ring_batch<KIND, VAR, true>(a, db, x, o.out_width);
+// allocator's target of the one-sample instantiations.  Left to itself it gave
+// their emission ones 81 VGPRs, one over the class, for the lanes of an SGPR it
+// moved to a VGPR: a batch reads its frame's constants through db.f[z] and
+// holds more scalars (106) than the one-frame kernel (100).  With the target
+// they take 80, the others are unchanged, and none uses scratch;
+// profiles/disk_ring_batch_isa.txt.  The GEO_FLAG_SS4 instantiations, a lane
+// per sample of the 2W x 2H ring render, have no target: 0.)
+template <int KIND, Shade SHADE, bool SS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SS ? 0 : 6))) void geo_render_disk_ring_batch_kernel(
+    const RenderArgs a, const DiskBatchArgs db, const geo::BandConsts* bands, const ShadeBatchArg<SHADE> eb,
+    const SsPitch<SS> o) {
+    disk_ring_batch<KIND, SHADE, SS>(a, db, bands, eb, o.width());
 }
 
 
@@ -1974,70 +1863,97 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_kernel<GEO_MODE_DIRECT, geo::kFlat, true, 1, false>;
     (void)geo_render_kernel<GEO_MODE_DIRECT, geo::kFlat, false, 1, false>;
     (void)geo_render_kernel<GEO_MODE_DIRECT, geo::kFlat, false, kMaxBatchFrames, false>;
-    (void)geo_render_disk_kernel<geo::kCurvedOut>;
-    (void)geo_render_disk_kernel<geo::kCurvedIn>;
-    (void)geo_render_disk_kernel<geo::kFlat>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDisk, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDisk, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDisk, GEO_MODE_DIRECT>;
     (void)geo_assemble_kernel<uint4>;
     (void)geo_assemble_kernel<uint32_t>;
     (void)geo_assemble_lead_kernel<true>;
     (void)geo_assemble_lead_kernel<false>;
-    (void)geo_render_disk_shift_kernel<geo::kCurvedOut>;
-    (void)geo_render_disk_shift_kernel<geo::kCurvedIn>;
-    (void)geo_render_disk_shift_kernel<geo::kFlat>;
-    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, true>;
-    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, true>;
-    (void)geo_render_disk_batch_kernel<geo::kFlat, true>;
-    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, false>;
-    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, false>;
-    (void)geo_render_disk_batch_kernel<geo::kFlat, false>;
-    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsPlain>;
-    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsPlain>;
-    (void)geo_render_ss_kernel<geo::kFlat, kSsPlain>;
-    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsDisk>;
-    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsDisk>;
-    (void)geo_render_ss_kernel<geo::kFlat, kSsDisk>;
-    (void)geo_render_ss_kernel<geo::kCurvedOut, kSsDiskShift>;
-    (void)geo_render_ss_kernel<geo::kCurvedIn, kSsDiskShift>;
-    (void)geo_render_ss_kernel<geo::kFlat, kSsDiskShift>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsPlain>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsPlain>;
-    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsPlain>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsDisk>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsDisk>;
-    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsDisk>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedOut, kSsDiskShift>;
-    (void)geo_render_ss_batch_kernel<geo::kCurvedIn, kSsDiskShift>;
-    (void)geo_render_ss_batch_kernel<geo::kFlat, kSsDiskShift>;
-    (void)geo_render_disk_emit_kernel<geo::kCurvedOut>;
-    (void)geo_render_disk_emit_kernel<geo::kCurvedIn>;
-    (void)geo_render_disk_emit_kernel<geo::kFlat>;
-    (void)geo_render_ss_emit_kernel<geo::kCurvedOut>;
-    (void)geo_render_ss_emit_kernel<geo::kCurvedIn>;
-    (void)geo_render_ss_emit_kernel<geo::kFlat>;
-    (void)geo_render_disk_emit_batch_kernel<geo::kCurvedOut>;
-    (void)geo_render_disk_emit_batch_kernel<geo::kCurvedIn>;
-    (void)geo_render_disk_emit_batch_kernel<geo::kFlat>;
-    (void)geo_render_ss_emit_batch_kernel<geo::kCurvedOut>;
-    (void)geo_render_ss_emit_batch_kernel<geo::kCurvedIn>;
-    (void)geo_render_ss_emit_batch_kernel<geo::kFlat>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, kDiskPlain>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, kDiskPlain>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, kDiskShift>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, kDiskShift>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, kDiskEmit>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, kDiskEmit>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskPlain>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskPlain>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskShift>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskShift>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, kDiskEmit>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, kDiskEmit>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskPlain>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskPlain>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskShift>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskShift>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedOut, kDiskEmit>;
-    (void)geo_render_ss_ring_batch_kernel<geo::kCurvedIn, kDiskEmit>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskShift, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDiskShift, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskShift, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDisk, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDisk, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, false, GEO_MODE_DIRECT>;
+    (void)geo_render_ss_sky_kernel<geo::kCurvedOut, 1>;
+    (void)geo_render_ss_sky_kernel<geo::kCurvedIn, 1>;
+    (void)geo_render_ss_sky_kernel<geo::kFlat, 1>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedOut, Shade::kDisk>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedIn, Shade::kDisk>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kFlat, Shade::kDisk>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskShift>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskShift>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kFlat, Shade::kDiskShift>;
+    (void)geo_render_ss_sky_kernel<geo::kCurvedOut, kMaxBatchFrames>;
+    (void)geo_render_ss_sky_kernel<geo::kCurvedIn, kMaxBatchFrames>;
+    (void)geo_render_ss_sky_kernel<geo::kFlat, kMaxBatchFrames>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDisk, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDisk, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskShift, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDiskEmit, GEO_MODE_DIRECT>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskEmit>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskEmit>;
+    (void)geo_render_ss_disk_frame_kernel<geo::kFlat, Shade::kDiskEmit>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskEmit, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDisk>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDisk>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskShift>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDisk, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kCurvedIn, Shade::kDisk, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_frame_kernel<geo::kFlat, Shade::kDisk, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskEmit, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskEmit, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskShift, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-"""GEO_FLAG_DISK on the device: geo_render_disk_kernel against the CPU path
+"""GEO_FLAG_DISK on the device: geo_render_disk_frame_kernel (Shade::kDisk) against the CPU path
 (geo_render_cpu_disk, the same header csrc/geo_disk.h) bit for bit, on whole
 frames, partial tiles and bands, under the learned dispatch order, and the
 C-ABI's rules (geo.h).  tests/test_disk_cpu.py ties the CPU path to geometry

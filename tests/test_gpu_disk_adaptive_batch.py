@@ -1,7 +1,7 @@
 """geo_render_disk_adaptive_batch: up to GEO_MAX_BATCH_FRAMES thin-disk frames in
-GEO_MODE_ADAPTIVE in one launch (geo_render_disk_adaptive_batch_kernel and its
-shifted, emission and SS4 siblings: wave_block_body with the adaptive
-integrator on DiskBatchFrame, the frame in blockIdx.z).  A one-sample frame is
+GEO_MODE_ADAPTIVE in one launch (geo_render_disk_batch_kernel's GEO_MODE_ADAPTIVE
+instantiations, plain, shifted and emission, one sample and SS4: wave_block_body
+with the adaptive integrator on DiskBatchFrame, the frame in blockIdx.z).  A one-sample frame is
 its one-frame geo_render_disk_adaptive render bit for bit, and so the CPU
 path's (geo_render_cpu_disk_adaptive); a GEO_FLAG_SS4 frame is the box resolve
 (numpy, below) of the one-frame render at twice the size, which no one-frame

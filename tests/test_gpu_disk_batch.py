@@ -1,5 +1,6 @@
 """geo_render_disk_batch: up to GEO_MAX_BATCH_FRAMES thin-disk frames in one
-launch (geo_render_disk_batch_kernel, the frame in blockIdx.z) draw, frame by
+launch (geo_render_disk_batch_kernel<KIND, Shade::kDisk | kDiskShift, false, GEO_MODE_DIRECT>,
+the frame in blockIdx.z) draw, frame by
 frame, the bytes geo_render_band_set draws for that frame and scene alone,
 unshaded and shaded (geo_set_disk_shift), and the bytes of the CPU path
 (geo_render_cpu_disk_shift, the same header csrc/geo_disk.h); the C-ABI's

@@ -1,5 +1,5 @@
 """Blackbody emission of the thin disk on the device:
-geo_render_disk_emit_kernel and geo_render_ss_emit_kernel against the CPU path
+geo_render_disk_frame_kernel and geo_render_ss_disk_frame_kernel (Shade::kDiskEmit) against the CPU path
 (geo_render_cpu_disk_emission, the same header csrc/geo_disk.h) bit for bit in
 every output and the g and q slots, for each integration kind, partial tiles,
 the three one-frame entry points and both dispatch orders; GEO_FLAG_SS4 against

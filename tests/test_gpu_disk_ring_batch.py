@@ -1,6 +1,6 @@
 """geo_render_disk_ring_batch: up to GEO_MAX_BATCH_FRAMES thin-disk frames with
 the capture band's pixels in f64 (geo_set_disk_ring_f64) in one render launch
-(geo_render_disk_ring_batch_kernel, and geo_render_ss_ring_batch_kernel with
+(geo_render_disk_ring_batch_kernel<KIND, SHADE, SS>, SS with
 GEO_FLAG_SS4; the frame in blockIdx.z, its band constants from the context's
 device table) draw, frame by frame, the bytes geo_render_band_set draws for
 that frame and scene alone with the state on, and the bytes of the CPU path
@@ -16,13 +16,13 @@ hit and the pixels whose colour the state changes: a batch that never reached
 the f64 arm cannot pass.  test_gpu_disk_batch's orbit has few such pixels and
 serves the layouts and the plumbing.
 
-Which instantiation runs where (KIND kCurvedOut / kCurvedIn; VAR plain / shift
-/ emit):
-  geo_render_disk_ring_batch_kernel<Out, plain|shift|emit>  test_batch_equals_single_frames, test_against_the_cpu_path
-  geo_render_disk_ring_batch_kernel<In, plain|emit>         test_batch_equals_single_frames[curved_in-*]
-  geo_render_disk_ring_batch_kernel<In, shift>              test_fuzzed_batches (seeds with a step outside kCurvedOut's)
-  geo_render_ss_ring_batch_kernel<Out, plain|shift|emit>    test_ss4_is_the_resolve
-  geo_render_ss_ring_batch_kernel<In, plain|shift|emit>     test_ss4_curved_in
+Which instantiation runs where (KIND kCurvedOut / kCurvedIn; SHADE plain / shift
+/ emit; SS false / true):
+  geo_render_disk_ring_batch_kernel<Out, plain|shift|emit, false>  test_batch_equals_single_frames, test_against_the_cpu_path
+  geo_render_disk_ring_batch_kernel<In, plain|emit, false>         test_batch_equals_single_frames[curved_in-*]
+  geo_render_disk_ring_batch_kernel<In, shift, false>              test_fuzzed_batches (seeds with a step outside kCurvedOut's)
+  geo_render_disk_ring_batch_kernel<Out, plain|shift|emit, true>   test_ss4_is_the_resolve
+  geo_render_disk_ring_batch_kernel<In, plain|shift|emit, true>    test_ss4_curved_in
 test_fuzzed_batches prints the (kind, variant, SS4) triples its seeds draw."""
 import math
 

@@ -1,5 +1,5 @@
 """Doppler and redshift shading of the thin disk on the device:
-geo_render_disk_shift_kernel against the CPU path (geo_render_cpu_disk_shift,
+geo_render_disk_frame_kernel (Shade::kDiskShift) against the CPU path (geo_render_cpu_disk_shift,
 the same header csrc/geo_disk.h) bit for bit in every output and the g slots,
 for each integration kind, a moving observer, partial tiles, a band set and
 both dispatch orders, and the C-ABI's state rules (geo.h).

@@ -1,6 +1,6 @@
 """geo_render_emission_batch: up to GEO_MAX_BATCH_FRAMES frames of the
 blackbody disk (geo_set_disk_emission) in one launch
-(geo_render_disk_emit_batch_kernel, and geo_render_ss_emit_batch_kernel with
+(geo_render_disk_batch_kernel with Shade::kDiskEmit, one sample or
 GEO_FLAG_SS4; the frame in blockIdx.z) draw, frame by frame, the bytes
 geo_render_band_set draws for that frame and scene alone, and the bytes of the
 CPU path (geo_render_cpu_disk_emission, the same header csrc/geo_disk.h); the

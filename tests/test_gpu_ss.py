@@ -1,5 +1,5 @@
-"""GEO_FLAG_SS4 on the device: geo_render_ss_kernel (the plain, the disk and
-the shifted disk frame) against the CPU path (tests/test_ss_cpu.py) byte for
+"""GEO_FLAG_SS4 on the device: geo_render_ss_sky_kernel (the plain frame) and
+geo_render_ss_disk_frame_kernel (the disk and the shifted disk frame) against the CPU path (tests/test_ss_cpu.py) byte for
 byte, against its own definition (the numpy resolve of the GPU's one-sample
 render at twice the size), on partial tiles, rows and bands, under the learned
 dispatch order, and the C-ABI's rules (geo.h)."""

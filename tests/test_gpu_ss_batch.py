@@ -1,5 +1,6 @@
 """geo_render_ss_batch: up to GEO_MAX_BATCH_FRAMES GEO_FLAG_SS4 frames in one
-launch (geo_render_ss_batch_kernel<KIND, VAR>, the frame in blockIdx.z) draw,
+launch (geo_render_ss_sky_kernel<KIND, kMaxBatchFrames> and, for disk scenes,
+geo_render_disk_batch_kernel<KIND, SHADE, true, GEO_MODE_DIRECT>; the frame in blockIdx.z) draw,
 frame by frame, the bytes geo_render_band_set draws for that frame and its SS
 scene alone (the plain, the disk and the shifted disk frame), the flag's own
 definition (the numpy box resolve of the one-sample render at twice the size)
@@ -7,12 +8,13 @@ and the bytes of the CPU path; the C-ABI's rules (geo.h) and
 dist.ShardedFrame's routing of supersampled batches.
 
 Which of the nine instantiations runs where (KIND kCurvedOut / kCurvedIn /
-kFlat = 0 / 1 / 2, VAR kSsPlain / kSsDisk / kSsDiskShift = 0 / 1 / 2): the
-orbit (rs 1, the observer outside the horizon) launches <0, 0>, <0, 1> and
-<0, 2> in every test parametrised by kind; test_flat_space_pan launches <2, 0>,
-<2, 1> and <2, 2> (rs 0); test_inside_the_horizon launches <1, 0>.  <1, 1> and
-<1, 2> cannot be reached through the C-ABI: GEO_FLAG_DISK refuses an observer
-at or inside the horizon (r_obs > rs unless rs == 0)."""
+kFlat; the plain frame, Shade::kDisk, Shade::kDiskShift): the orbit (rs 1, the
+observer outside the horizon) launches the three of kCurvedOut in every test
+parametrised by kind; test_flat_space_pan launches the three of kFlat (rs 0);
+test_inside_the_horizon launches the plain frame of kCurvedIn.  GEO_FLAG_DISK
+refuses an observer at or inside the horizon (r_obs > rs unless rs == 0), so
+the two disk instantiations of kCurvedIn run through a step above 1/2:
+tests/test_gpu_wave_block_matrix.py, which has a cell for every instantiation."""
 import ctypes
 import math
 
