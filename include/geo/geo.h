@@ -69,7 +69,9 @@ extern "C" {
                                    announced by GEO_HAS_DISK_ADAPTIVE:
                                    geo_render_disk_adaptive;
                                    announced by GEO_HAS_DISK_ADAPTIVE_BATCH:
-                                   geo_render_disk_adaptive_batch) */
+                                   geo_render_disk_adaptive_batch;
+                                   announced by GEO_HAS_DISK_ADAPTIVE_RING:
+                                   geo_render_disk_adaptive_ring) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -81,6 +83,7 @@ extern "C" {
 #define GEO_HAS_DISK_RING_BATCH 1
 #define GEO_HAS_DISK_ADAPTIVE 1
 #define GEO_HAS_DISK_ADAPTIVE_BATCH 1
+#define GEO_HAS_DISK_ADAPTIVE_RING 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -165,7 +168,8 @@ typedef enum geo_status {
                                    observer's frames); geo_render_band_set_frames / _batch
                                    refuse the flag.  GEO_MODE_DIRECT (GEO_MODE_ADAPTIVE
                                    through geo_render_disk_adaptive, whose comment states
-                                   the crossing rule of that mode, and
+                                   the crossing rule of that mode,
+                                   geo_render_disk_adaptive_ring and
                                    geo_render_disk_adaptive_batch alone),
                                    with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
                                    and rs < r_in; r_out < sphere_r and r_obs < sphere_r
@@ -344,7 +348,8 @@ int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
  * renders, geo_render_disk_batch, geo_render_ss_batch and
  * geo_render_emission_batch (such a frame would come out without its band);
  * geo_render_disk_ring_batch (GEO_HAS_DISK_RING_BATCH) draws batched and
- * GEO_FLAG_SS4 disk frames with the band.
+ * GEO_FLAG_SS4 disk frames with the band, and geo_render_disk_adaptive_ring
+ * (GEO_HAS_DISK_ADAPTIVE_RING) one GEO_MODE_ADAPTIVE disk frame with it.
  * Renders without GEO_FLAG_DISK are untouched, and GEO_FLAG_DISK |
  * GEO_FLAG_RING_F64 stays GEO_EINVAL everywhere.  Off by default; kept across
  * geo_set_disk, cleared by geo_clear_disk.  GEO_EINVAL for a NULL ctx. */
@@ -720,13 +725,77 @@ int geo_render_disk_ring_batch(geo_ctx* ctx, const geo_frame* frames, const geo_
  * a grid key of its own; a tile's cost is in attempts) and geo_set_tile_order
  * work as for the one-frame direct render.  Batched adaptive disk frames, the
  * multi-GPU pipeline's and GEO_FLAG_SS4 with the adaptive disk go through
- * geo_render_disk_adaptive_batch (this call keeps refusing the flag).  Not in
- * this ABI: the f64 capture band with the adaptive disk.  Every older call
- * keeps every refusal it has.  Asynchronous on `stream`. */
+ * geo_render_disk_adaptive_batch (this call keeps refusing the flag); one
+ * adaptive disk frame with its f64 capture band goes through
+ * geo_render_disk_adaptive_ring (this call keeps refusing that state).  Every
+ * older call keeps every refusal it has.  Asynchronous on `stream`. */
 int geo_render_disk_adaptive(geo_ctx* ctx, const geo_frame* frame, const geo_scene* scene, uint32_t width,
                              uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
                              uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
                              uint32_t* out_steps, unsigned long long* steps_total, void* stream);
+
+/* The adaptive disk with its capture band in f64 (GEO_HAS_DISK_ADAPTIVE_RING):
+ * one GEO_MODE_ADAPTIVE | GEO_FLAG_DISK frame (GEO_FLAG_DEFER_STEPS at most
+ * beside it) of the context's disk, unshaded, with geo_set_disk_shift or with
+ * geo_set_disk_emission as the context has it, with the state of
+ * geo_set_disk_ring_f64 on.  The prototype, the layouts (a band set, or a row
+ * range as the one-band case) and the output rules are
+ * geo_render_disk_adaptive's; all per-pixel outputs are written: colour, mask,
+ * UV, steps, and the buffers armed by geo_disk_hits_next_render,
+ * geo_disk_shift_next_render and geo_disk_emission_next_render.
+ * Per pixel: a pixel of the band |b/b_c - 1| < GEO_RING_X (GEO_FLAG_RING_F64's
+ * band, decided on the f32 ray as in every ring render) skips the adaptive
+ * loop and takes its traveled angle, mask, step count and the three crossing
+ * probes from the f64 path of geo_set_disk_ring_f64 (csrc/geo_band.h
+ * band_lambda_disk), with the scene's step and max_steps as that loop's fixed
+ * step and budget, as in a plain GEO_MODE_ADAPTIVE | GEO_FLAG_RING_F64 render;
+ * tol is not read there.  Every other pixel is geo_render_disk_adaptive's.
+ * Three properties follow, and the tests hold the call to them:
+ *   1. outside the band every output of a pixel equals that of
+ *      geo_render_disk_adaptive for the same call with the state off, bit for
+ *      bit;
+ *   2. inside the band every output of a pixel, steps included, equals that of
+ *      the GEO_MODE_DIRECT ring render of the same scene (geo_render_band_set
+ *      with the state on, the same rs, sphere_r, r_obs, step and max_steps),
+ *      bit for bit: the band's arithmetic does not depend on the mode;
+ *   3. mask, UV, steps and steps_total of the frame equal those of the plain
+ *      GEO_MODE_ADAPTIVE render of the scene with GEO_FLAG_RING_F64 in place
+ *      of GEO_FLAG_DISK.
+ * steps_total (or the deferred accumulator) therefore mixes units, as that
+ * plain render's does: adaptive attempts outside the band, fixed f64 steps
+ * inside it.  On the 96 x 54 test pose whose band holds 2212 pixels the frame
+ * counts 663738 against 161635 attempts with the state off.
+ * Accuracy: in the band the hit radii are the f64 integrator's rounded once to
+ * f32, the direct ring render's: on that pose the largest relative radius error
+ * against the f64 integration of tests/disk_ref.py falls from 9.1e-4 (the
+ * adaptive disk, state off, in the band; 1.25e-3 for the direct disk with the
+ * state off) to 2.11e-6.  Outside the band the radii stay
+ * geo_render_disk_adaptive's: up to 1.95e-4 just outside it on the fuzzed
+ * scenes (0.02 <= |b/b_c - 1| < 0.05, tol 1e-6).  On the MI355X the kernels'
+ * own buffers on 18 fuzzed scenes (472 in-band slots, none dropped) differ
+ * from the f64 answer by at most: radius 9.71e-07 (0.23 of its bar), azimuth
+ * 7.15e-08 turns (0.13), g 1.06e-06 (0.14), q 4.85e-06 (0.16)
+ * (tests/disk_band_truth.py's bars; profiles/disk_adaptive_ring_truth_gpu.txt).
+ * GEO_ESTATE with the state off (the call has nothing to draw that
+ * geo_render_disk_adaptive does not), without a sky or a disk.  With rs == 0
+ * there is no capture orbit: the state is ignored and the frame is
+ * geo_render_disk_adaptive's, kernel and bytes.  GEO_EINVAL for a
+ * GEO_MODE_DIRECT or GEO_MODE_FAN scene, for any flag beside GEO_FLAG_DISK and
+ * GEO_FLAG_DEFER_STEPS (GEO_FLAG_SS4, _MIPS, _COMPOSITE and _RING_F64
+ * included), and wherever geo_render_disk_adaptive's disk, shift, emission or
+ * tol rules are broken.  A refused call launches nothing, writes nothing and
+ * consumes the armed buffers and the timing pair.  geo_time_next_render,
+ * geo_set_dispatch (the learned order has a grid key of its own: the mode and
+ * the band bit; a tile's cost is its waves' largest count of attempts plus
+ * twice their largest count of f64 steps) and geo_set_tile_order work as for
+ * geo_render_disk_adaptive.  Not in this ABI: batched frames and GEO_FLAG_SS4
+ * with the adaptive band (an adaptive sibling of geo_render_disk_ring_batch)
+ * and with it the multi-GPU pipeline's route for such a scene.  Every older
+ * call keeps every refusal it has.  Asynchronous on `stream`. */
+int geo_render_disk_adaptive_ring(geo_ctx* ctx, const geo_frame* frame, const geo_scene* scene, uint32_t width,
+                                  uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                                  uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
+                                  uint32_t* out_steps, unsigned long long* steps_total, void* stream);
 
 /* geo_render_band_set_batch for the thin disk in GEO_MODE_ADAPTIVE
  * (GEO_HAS_DISK_ADAPTIVE_BATCH): nframes (1 .. GEO_MAX_BATCH_FRAMES)
@@ -765,9 +834,10 @@ int geo_render_disk_adaptive(geo_ctx* ctx, const geo_frame* frame, const geo_sce
  * costs, a tile's cost being in attempts; the learned order's key holds the
  * mode beside the disk, SS and emission bits; under GEO_FLAG_SS4 the grid is
  * the sample frame's).  Not in this ABI: per-pixel outputs from a batch, and
- * the f64 capture band with the adaptive disk.  Every older call keeps every
- * refusal it has.  One scene for every frame: pass copies.  Asynchronous on
- * `stream`. */
+ * the f64 capture band in a batch of adaptive disk frames or under
+ * GEO_FLAG_SS4 (geo_render_disk_adaptive_ring draws one one-sample frame with
+ * it).  Every older call keeps every refusal it has.  One scene for every
+ * frame: pass copies.  Asynchronous on `stream`. */
 int geo_render_disk_adaptive_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
                                    uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                                    uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,

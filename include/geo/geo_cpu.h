@@ -138,6 +138,28 @@ int geo_render_cpu_disk_adaptive(const geo_frame* frame, const geo_scene* scene,
                                  const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q,
                                  const geo_disk_shift* shift);
 
+/* geo_render_cpu_disk_adaptive with the state of geo_set_disk_ring_f64 as a
+ * trailing argument (geo.h, geo_render_disk_adaptive_ring,
+ * GEO_HAS_DISK_ADAPTIVE_RING): ring_f64 != 0 takes the band's lanes
+ * (|b/b_c - 1| < GEO_RING_X on the f32 ray) through the f64 path of
+ * csrc/geo_band.h with the scene's step and max_steps as its fixed step and
+ * budget, and every other lane through the adaptive integrator, under the
+ * device's rules (rs = 0 ignores it).  ring_f64 == 0 is
+ * geo_render_cpu_disk_adaptive.  Output equal to the GPU's bit for bit.  The
+ * statuses differ from the device's where this path has no context: a NULL
+ * disk is GEO_EINVAL here, as in every geo_render_cpu_disk* function (the
+ * device call returns GEO_ESTATE while no disk is set), and ring_f64 == 0
+ * draws the state-off frame where the device call returns GEO_ESTATE. */
+int geo_render_cpu_disk_adaptive_ring_f64(const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8,
+                                          uint32_t sky_w, uint32_t sky_h, const float* fan, uint32_t n_fan,
+                                          uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+                                          uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask,
+                                          float* out_uv, uint32_t* out_steps, unsigned long long* steps_total,
+                                          const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+                                          uint32_t disk_h, float* out_hits, const geo_disk_emission* emission,
+                                          const uint8_t* ramp_rgba8, uint32_t n, float* out_g, float* out_q,
+                                          const geo_disk_shift* shift, int ring_f64);
+
 #ifdef __cplusplus
 }
 #endif

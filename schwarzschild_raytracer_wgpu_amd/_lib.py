@@ -44,6 +44,7 @@ GEO_HAS_DISK_RING_F64 = 1  # geo_set_disk_ring_f64
 GEO_HAS_DISK_RING_BATCH = 1  # geo_render_disk_ring_batch
 GEO_HAS_DISK_ADAPTIVE = 1  # geo_render_disk_adaptive
 GEO_HAS_DISK_ADAPTIVE_BATCH = 1  # geo_render_disk_adaptive_batch
+GEO_HAS_DISK_ADAPTIVE_RING = 1  # geo_render_disk_adaptive_ring
 GEO_DISK_PROFILE_POWER = 0
 GEO_DISK_PROFILE_THIN = 1
 GEO_DISK_RAMP_MAX = 1024
@@ -188,6 +189,11 @@ SIGNATURES = {
          ctypes.c_size_t, _vp, _vp],
     ),
     "geo_render_disk_adaptive": (
+        _int,
+        [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _vp,
+         _vp, _vp, _vp, _vp, _vp],
+    ),
+    "geo_render_disk_adaptive_ring": (
         _int,
         [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _vp,
          _vp, _vp, _vp, _vp, _vp],

@@ -407,6 +407,20 @@ class Context:
             _ptr(out_rgba), _ptr(out_mask), _ptr(out_uv), _ptr(out_steps), _ptr(steps_total),
             _stream_handle(stream)))
 
+    def render_disk_adaptive_ring(self, frame: GeoFrame, scene: GeoScene, width: int, height: int, band_rows: int,
+                                  row0: int, row_stride: int, nbands: int, out_rgba, out_mask=None, out_uv=None,
+                                  out_steps=None, steps_total=None, stream=None) -> None:
+        """geo_render_disk_adaptive_ring: render_disk_adaptive's frame with the capture band's pixels through
+        the f64 path (set_disk_ring_f64 must be on: GEO_ESTATE otherwise; rs == 0 ignores it), the same layout
+        and outputs.  Outside the band a pixel is render_disk_adaptive's, inside it the direct ring render's,
+        bit for bit; steps_total mixes adaptive attempts and the band's fixed f64 steps."""
+        nrows = nbands * band_rows
+        _check_outputs(nrows, width, out_rgba, out_mask, out_uv, out_steps, steps_total)
+        check("geo_render_disk_adaptive_ring", lib.geo_render_disk_adaptive_ring(
+            self._h, ctypes.byref(frame), ctypes.byref(scene), width, height, band_rows, row0, row_stride, nbands,
+            _ptr(out_rgba), _ptr(out_mask), _ptr(out_uv), _ptr(out_steps), _ptr(steps_total),
+            _stream_handle(stream)))
+
     def render_disk_adaptive_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int,
                                    row_stride: int, nbands: int, out_rgba, frame_stride: int | None = None,
                                    steps_total=None, stream=None) -> None:

@@ -196,8 +196,10 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
                 geo::disk_ray(j.dk, k, c2x, c2y, ct, rct, &dr);
             uint32_t n = 0;
             if (j.dring) {
-                // geo_render_disk_ring_kernel per pixel: the band's lanes by
-                // the f64 path, the others as below, both through DiskHits
+                // geo_render_disk_ring_kernel per pixel
+                // (geo_render_disk_adaptive_ring_kernel with j.dadaptive): the
+                // band's lanes by the f64 path, the others as below, both
+                // through DiskHits
                 float lam;
                 bool bh;
                 geo::DiskHits h;
@@ -207,9 +209,14 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
                     bh = l < (double)geo::kBlackHoleLambda;
                 } else {
                     float Uk[geo::kDiskMaxCrossings];
-                    const float ang = geo::geodesic_kind(k) == geo::kCurvedOut
-                                          ? geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk)
-                                          : geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
+                    const bool out = geo::geodesic_kind(k) == geo::kCurvedOut;
+                    float ang;
+                    if (j.dadaptive)
+                        ang = out ? geo::geodesic_angle_adaptive_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk)
+                                  : geo::geodesic_angle_adaptive_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
+                    else
+                        ang = out ? geo::geodesic_angle_disk<geo::kCurvedOut>(k, st, ct, rct, dr, &n, Uk)
+                                  : geo::geodesic_angle_disk<geo::kCurvedIn>(k, st, ct, rct, dr, &n, Uk);
                     lam = geo::kPi2 - ang;
                     bh = lam < geo::kBlackHoleLambda;
                     geo::disk_hits_f32(j.dk, k, dr, Uk, n, ang, &h);
@@ -670,4 +677,19 @@ extern "C" int geo_render_cpu_disk_adaptive(const geo_frame* frame, const geo_sc
                            threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
                            disk_h, out_hits, emission ? nullptr : shift, emission || shift ? out_g : nullptr, emission,
                            ramp_rgba8, n, emission ? out_q : nullptr, false, true);
+}
+
+extern "C" int geo_render_cpu_disk_adaptive_ring_f64(
+    const geo_frame* frame, const geo_scene* scene, const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+    const float* fan, uint32_t n_fan, uint32_t width, uint32_t height, uint32_t row0, uint32_t nrows,
+    uint32_t row_step, int threads, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
+    unsigned long long* steps_total, const geo_disk* disk, const uint8_t* disk_rgba8, uint32_t disk_w,
+    uint32_t disk_h, float* out_hits, const geo_disk_emission* emission, const uint8_t* ramp_rgba8, uint32_t n,
+    float* out_g, float* out_q, const geo_disk_shift* shift, int ring_f64) {
+    if (!disk) return GEO_EINVAL;
+    // (geo_render_cpu_disk_adaptive with the band's lanes through the f64 path: run_rows_disk's ring branch)
+    return render_cpu_impl(frame, scene, sky_rgba8, sky_w, sky_h, fan, n_fan, width, height, row0, nrows, row_step,
+                           threads, out_rgba8, out_mask, out_uv, out_steps, steps_total, disk, disk_rgba8, disk_w,
+                           disk_h, out_hits, emission ? nullptr : shift, emission || shift ? out_g : nullptr, emission,
+                           ramp_rgba8, n, emission ? out_q : nullptr, ring_f64 != 0, true);
 }

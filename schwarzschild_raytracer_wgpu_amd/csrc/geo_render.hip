@@ -808,7 +808,10 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // more; a GEO_FLAG_SS4 render too: its grid is the sample frame's; an
     // emission render has a key of its own, as the disk render has, and a
     // disk render with geo_set_disk_ring_f64 on, for its band's tiles, one
-    // frame or geo_render_disk_ring_batch's, whose frame 0 records them)
+    // frame or geo_render_disk_ring_batch's, whose frame 0 records them;
+    // geo_render_disk_adaptive_ring shares a key with neither the adaptive
+    // disk render, which has no disk_ring bit, nor the direct ring render,
+    // whose mode differs)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
                              (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u) |
                                  (w.emit ? 16u : 0u) | (w.disk_ring ? 32u : 0u),
@@ -896,7 +899,9 @@ static DiskEmitArgs emit_args(const geo_ctx* c, const RenderCall& rc, const Rend
 // buffer armed; the disk's constants do not depend on the resolution), or
 // with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel:
 // the band's constants ride as a further argument; the curved kinds only, a
-// capture orbit needs rs > 0).  The rules let no adaptive SS4 frame through.
+// capture orbit needs rs > 0), or adaptive with it on
+// (geo_render_disk_adaptive_ring: geo_render_disk_adaptive_ring_kernel, the
+// same arguments).  The rules let no adaptive SS4 frame through.
 static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskArgs d;
     if (!geo::disk_consts(rc.frames[0].central_to_uv, c->disk.normal, c->disk.axis, c->disk.r_in, c->disk.r_out, w.a.k,
@@ -920,8 +925,13 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
                 x.out_g = w.out_g;
             }
             if (w.disk_ring) {
-                if constexpr (KIND != geo::kFlat)
+                if constexpr (KIND != geo::kFlat) {
+                    // (adaptive: geo_render_disk_adaptive_ring alone; the rules refuse the older calls)
+                    if (w.adaptive)
+                        return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_adaptive_ring_kernel<KIND, SHADE>, fb, d,
+                                                  x, bk);
                     return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_ring_kernel<KIND, SHADE>, fb, d, x, bk);
+                }
                 return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
             }
             if (w.ss)
@@ -1426,6 +1436,14 @@ int geo_render_disk_adaptive(geo_ctx* c, const geo_frame* frame, const geo_scene
                              uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
                              unsigned long long* steps_total, void* stream) {
     return render_frame(Entry::kDiskAdaptive, c, frame, scene, width, height, band_rows, row0, row_stride, nbands,
+                        out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
+}
+
+int geo_render_disk_adaptive_ring(geo_ctx* c, const geo_frame* frame, const geo_scene* scene, uint32_t width,
+                                  uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
+                                  uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
+                                  uint32_t* out_steps, unsigned long long* steps_total, void* stream) {
+    return render_frame(Entry::kDiskAdaptiveRing, c, frame, scene, width, height, band_rows, row0, row_stride, nbands,
                         out_rgba8, out_mask, out_uv, out_steps, steps_total, stream);
 }
 

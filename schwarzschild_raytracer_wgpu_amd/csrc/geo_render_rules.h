@@ -37,8 +37,9 @@ enum class Entry : uint8_t {
     kEmissionBatch,      // geo_render_emission_batch
     kDiskRingBatch,      // geo_render_disk_ring_batch
     kDiskAdaptiveBatch,  // geo_render_disk_adaptive_batch
+    kDiskAdaptiveRing,   // geo_render_disk_adaptive_ring
 };
-constexpr int kEntries = 11;
+constexpr int kEntries = 12;
 
 enum class Ss : uint8_t { kNo, kOneFrame, kAnyFrames };  // GEO_FLAG_SS4: refused, drawn alone, drawn in any batch
 enum class Needs : uint8_t { kAnyScene, kDiskScene, kSsScene };
@@ -73,6 +74,7 @@ constexpr EntryTraits kEntryTraits[kEntries] = {
     {true, GEO_MODE_DIRECT, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kEmission, true, Band::kNo, true, true},
     {true, GEO_MODE_DIRECT, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kRing, true, Band::kAll, true, true},
     {true, GEO_MODE_ADAPTIVE, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kNone, true, Band::kNoOrbit, true, true},
+    {true, GEO_MODE_ADAPTIVE, Ss::kNo, Needs::kDiskScene, NeedsState::kRing, true, Band::kAll, false, false},
 };
 constexpr const EntryTraits& traits(Entry e) { return kEntryTraits[(int)e]; }
 
@@ -150,7 +152,8 @@ static inline void set_call(RenderCall& rc, Entry e, const geo_frame* frames, co
 // false (GEO_EINVAL).  g0 .. g3 are the entry point's own four row arguments
 // in its order: (row0, nrows) for geo_render_rows, (band_rows, band0,
 // band_step, nbands) for geo_render_bands, (band_rows, row0, row_stride,
-// nbands) for geo_render_band_set and geo_render_disk_adaptive.
+// nbands) for geo_render_band_set, geo_render_disk_adaptive and
+// geo_render_disk_adaptive_ring.
 static inline bool frame_call(RenderCall& rc, Entry e, const void* c, const geo_frame* frame, const geo_scene* scene,
                               uint32_t width, uint32_t height, uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3,
                               uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv, uint32_t* out_steps,
@@ -176,10 +179,10 @@ static inline bool frame_call(RenderCall& rc, Entry e, const void* c, const geo_
     } else {
         const uint32_t row_stride = g2, nbands = g3;
         row0 = g1, nrows = g0;
-        // geo_render_disk_adaptive: a row range is the one-band case: any
-        // number of rows, as one band that covers them all
-        // (geo_render_rows' mapping; row_stride is not read)
-        const bool one_band = e == Entry::kDiskAdaptive && nbands == 1;
+        // geo_render_disk_adaptive and geo_render_disk_adaptive_ring: a row
+        // range is the one-band case: any number of rows, as one band that
+        // covers them all (geo_render_rows' mapping; row_stride is not read)
+        const bool one_band = (e == Entry::kDiskAdaptive || e == Entry::kDiskAdaptiveRing) && nbands == 1;
         const bool rows = one_band && nrows != 0 && nrows <= (1u << 20) && width != 0 && height != 0 &&
                           width <= (1u << 20) && height <= (1u << 20) && row0 < height;
         if (!rows && !band_set_ok(width, height, g0, row0, row_stride, nbands)) return GEO_RULE(9), false;
@@ -219,9 +222,10 @@ static inline int check_scene(const RuleState& c, const RenderCall& rc, RenderRu
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
                           GEO_FLAG_DISK | GEO_FLAG_SS4)) != 0)
         return GEO_RULE(13), GEO_EINVAL;
-    // geo_render_disk_adaptive and geo_render_disk_adaptive_batch draw
-    // GEO_MODE_ADAPTIVE disk scenes only, DISK with DEFER_STEPS (and SS4, the
-    // batch) at most (the older calls draw the direct and fan scenes)
+    // geo_render_disk_adaptive, geo_render_disk_adaptive_ring and
+    // geo_render_disk_adaptive_batch draw GEO_MODE_ADAPTIVE disk scenes only,
+    // DISK with DEFER_STEPS (and SS4, the batch) at most (the older calls draw
+    // the direct and fan scenes)
     if (t.mode == GEO_MODE_ADAPTIVE &&
         (scene->mode != GEO_MODE_ADAPTIVE ||
          (scene->flags & ~(GEO_FLAG_DEFER_STEPS | (t.ss == Ss::kNo ? 0u : GEO_FLAG_SS4))) != GEO_FLAG_DISK))

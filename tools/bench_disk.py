@@ -112,6 +112,25 @@ counts as a gain where it is faster than the one-frame side by more than twice
 that side's alternation spread.
 
   python tools/bench_disk.py --batch 8 --adaptive [--out profiles/disk_adaptive_batch_bench.json]
+
+--adaptive --ring measures the adaptive disk frame with the capture band in f64
+(geo_render_disk_adaptive_ring, geo_set_disk_ring_f64 on) against the same frame
+with the state off (geo_render_disk_adaptive) on --adaptive's scene, by --ring's
+method, each kind on its own context: --alternations (5) times --n (30)
+event-timed dispatches of each kind in blocks, after --settle (4) alternations
+of the same form that are reported apart, --sessions (2) sessions.  The plain
+adaptive frame with and without GEO_FLAG_RING_F64 runs beside them in the same
+alternations: the plain frame's own ring cost is the second yardstick.  Per
+session it reports the medians over the alternations, on over off and ring over
+plain, each off side's spread ((max - min) / median of its alternation medians)
+and whether each cost lies beyond twice that spread.  One JSON object.
+With --camera-away the camera is turned by pi, away from the hole: no pixel of
+the frame lies in the band (steps_total_on then equals attempts_total_off), so
+on over off is the cost of the ring kernel's shape alone, its registers and the
+LDS copy, on lanes that all take the f32 path.
+
+  python tools/bench_disk.py --adaptive --ring [--out profiles/disk_adaptive_ring_bench.json]
+  python tools/bench_disk.py --adaptive --ring --camera-away [--out profiles/disk_adaptive_ring_away_bench.json]
 """
 from __future__ import annotations
 
@@ -147,22 +166,38 @@ def main():
     p.add_argument("--shaded-first", action="store_true",
                    help="with --batch K --emission: the shaded batch is each sample's first launch, the emission "
                         "batch its last (default: the other way round)")
+    p.add_argument("--camera-away", action="store_true",
+                   help="with --adaptive --ring: the camera turned away from the hole, a frame with no band pixel")
     p.add_argument("--out")
     args = p.parse_args()
-    if args.adaptive and (args.ring or args.emission or args.shift):
-        raise SystemExit("--adaptive goes alone, or with --batch K")
+    if args.adaptive and (args.emission or args.shift or (args.ring and args.batch)):
+        raise SystemExit("--adaptive goes alone, with --ring, or with --batch K")
     if not args.out:
-        name = "disk_adaptive_batch_bench.json" if (args.adaptive and args.batch) else "disk_adaptive_bench.json" if args.adaptive else "disk_ring_batch_bench_cfg3.json" if (args.batch and args.ring) else "disk_ring_bench_cfg3.json" if (
-            args.ring) else "disk_emission_batch_bench_cfg3.json" if (
-            args.batch and args.emission) else (
-            "disk_batch_bench_cfg3.json") if args.batch else (
-            "disk_emission_bench_cfg3.json" if args.emission else (
-                "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json"))
+        if args.adaptive and args.batch:
+            name = "disk_adaptive_batch_bench.json"
+        elif args.adaptive and args.ring:
+            name = "disk_adaptive_ring_away_bench.json" if args.camera_away else "disk_adaptive_ring_bench.json"
+        elif args.adaptive:
+            name = "disk_adaptive_bench.json"
+        elif args.batch and args.ring:
+            name = "disk_ring_batch_bench_cfg3.json"
+        elif args.ring:
+            name = "disk_ring_bench_cfg3.json"
+        elif args.batch and args.emission:
+            name = "disk_emission_batch_bench_cfg3.json"
+        elif args.batch:
+            name = "disk_batch_bench_cfg3.json"
+        elif args.emission:
+            name = "disk_emission_bench_cfg3.json"
+        else:
+            name = "disk_shift_bench_cfg3.json" if args.shift else "disk_bench_cfg3.json"
         args.out = os.path.join(ROOT, "profiles", name)
     if args.n < 20:
         raise SystemExit("--n must be at least 20")
     if args.adaptive and args.batch:
         return adaptive_batch_main(args)
+    if args.adaptive and args.ring:
+        return adaptive_ring_main(args)
     if args.adaptive:
         return adaptive_main(args)
     if args.batch and args.ring:
@@ -571,6 +606,134 @@ def adaptive_main(args):
                   "process, each kind on its own context; spread = (max - min) / median of a kind's alternation "
                   "medians; a surplus is a figure only beyond twice the plain adaptive side's spread",
         "sessions": [adaptive_session(args, cfg, frame, scenes, sky, tex) for _ in range(args.sessions)],
+    }
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
+def adaptive_ring_session(args, cfg, frame, scenes, sky, tex):
+    import numpy as np
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd.timing import HipEvent
+
+    W, H = cfg.width, cfg.height
+    # (each kind on its own context: the learned dispatch order is kept per context)
+    ctxs = {}
+    for kind in ("disk_off", "disk_on", "plain", "plain_ring"):
+        c = g.Context(0)
+        c.set_sky(sky)
+        if kind.startswith("disk"):
+            c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
+            c.set_disk_ring_f64(kind == "disk_on")
+        ctxs[kind] = c
+    dev = torch.device("cuda:0")
+    out = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)
+
+    def run(kind, total=None):
+        c = ctxs[kind]
+        if kind == "disk_on":
+            c.render_disk_adaptive_ring(frame, scenes["disk"], W, H, H, 0, H, 1, out, None, None, None, total)
+        elif kind == "disk_off":  # (the parent's kernel)
+            c.render_disk_adaptive(frame, scenes["disk"], W, H, H, 0, H, 1, out, None, None, None, total)
+        else:
+            c.render_rows(frame, scenes[kind], W, H, 0, H, out, None, None, None, total)
+
+    for _ in range(args.warmup):
+        for kind in ctxs:
+            run(kind)
+    torch.cuda.synchronize()
+    blocks, settling = [], []
+    for alt in range(args.settle + args.alternations):
+        med = {}
+        for kind, c in ctxs.items():
+            ev = []
+            for _ in range(args.n):
+                a, b = HipEvent(), HipEvent()
+                c.time_next_render(a, b)
+                run(kind)
+                ev.append((a, b))
+            torch.cuda.synchronize()
+            ms = np.array([a.elapsed_time(b) for a, b in ev])
+            med[kind + "_ms_median"] = float(np.median(ms))
+            med[kind + "_ms_min"] = float(ms.min())
+            med[kind + "_ms_iqr"] = float(np.subtract(*np.percentile(ms, [75, 25])))
+        med["disk_on_over_off"] = med["disk_on_ms_median"] / med["disk_off_ms_median"]
+        med["plain_ring_over_plain"] = med["plain_ring_ms_median"] / med["plain_ms_median"]
+        (settling if alt < args.settle else blocks).append(med)
+    # what the two disk frames draw (two more renders, untimed): the state-on frame's hits, both step totals
+    hits = torch.zeros(W * H * 6, dtype=torch.float32, device=dev)
+    total_on = torch.zeros(1, dtype=torch.int64, device=dev)
+    total_off = torch.zeros(1, dtype=torch.int64, device=dev)
+    ctxs["disk_on"].disk_hits_next_render(hits)
+    run("disk_on", total_on)
+    run("disk_off", total_off)
+    torch.cuda.synchronize()
+    hv = hits.view(H, W, 3, 2)[..., 0] > 0
+    for c in ctxs.values():
+        c.close()
+    m = {k: np.array([b[k + "_ms_median"] for b in blocks]) for k in ctxs}
+    spread = {k: float((m[k].max() - m[k].min()) / np.median(m[k])) for k in ("disk_off", "plain")}
+    on_off = float(np.median(m["disk_on"]) / np.median(m["disk_off"]))
+    ring_plain = float(np.median(m["plain_ring"]) / np.median(m["plain"]))
+    return {
+        "settling_alternations_not_counted": settling, "alternations": blocks,
+        **{k + "_ms_median": float(np.median(v)) for k, v in m.items()},
+        "disk_on_over_off": on_off,
+        "disk_on_over_off_min": float(min(b["disk_on_over_off"] for b in blocks)),
+        "disk_on_over_off_max": float(max(b["disk_on_over_off"] for b in blocks)),
+        "disk_off_alternation_spread": spread["disk_off"],
+        "disk_cost_beyond_twice_the_spread": bool(abs(on_off - 1.0) > 2.0 * spread["disk_off"]),
+        "plain_ring_over_plain": ring_plain,
+        "plain_alternation_spread": spread["plain"],
+        "plain_cost_beyond_twice_the_spread": bool(abs(ring_plain - 1.0) > 2.0 * spread["plain"]),
+        "hit_pixels_per_slot": [int(hv[..., k].sum()) for k in range(3)],
+        # (mixed units with the state on: adaptive attempts outside the band, fixed f64 steps inside it)
+        "steps_total_on": int(total_on.item()), "attempts_total_off": int(total_off.item()),
+    }
+
+
+def adaptive_ring_main(args):
+    import math
+
+    import torch
+
+    import schwarzschild_raytracer_wgpu_amd as g
+    from schwarzschild_raytracer_wgpu_amd import _lib
+    from schwarzschild_raytracer_wgpu_amd.scenes import CONFIGS, make_disk_texture, make_sky
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_disk.py needs a HIP device")
+    cfg, cfg5 = CONFIGS["cfg3_4k"], CONFIGS["cfg5_8k_adaptive"]
+    obs = g.Observer(cfg.rs, cfg.fov, cfg.width, cfg.height)
+    obs.set_position(*cfg.position)
+    obs.set_camera(cfg.camera[0] + (math.pi if args.camera_away else 0.0), cfg.camera[1])
+    obs.set_energy(cfg.energy)
+    frame = obs.calc_transformation_pipeline()
+    r = obs.get_radial_position()
+    A = _lib.GEO_MODE_ADAPTIVE
+    scenes = {
+        "plain": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg5.step, cfg5.max_steps, A, 0, cfg5.tol),
+        "plain_ring": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg5.step, cfg5.max_steps, A, _lib.GEO_FLAG_RING_F64,
+                                   cfg5.tol),
+        "disk": g.make_scene(cfg.rs, cfg.sphere_r, r, cfg5.step, cfg5.max_steps, A, _lib.GEO_FLAG_DISK, cfg5.tol),
+    }
+    sky, tex = make_sky(cfg.sky, cfg.sky_size), make_disk_texture((1024, 128))
+    res = {
+        "config": "cfg3_4k's scene at cfg5_8k_adaptive's mode, step and tol" + (
+            ", the camera turned by pi (no band pixel)" if args.camera_away else ""),
+        "width": cfg.width, "height": cfg.height,
+        "step": cfg5.step, "tol": cfg5.tol, "max_steps": cfg5.max_steps, "disk": [1.6 * cfg.rs, 2.2 * cfg.rs],
+        "n": args.n, "alternations": args.alternations, "settle": args.settle, "warmup": args.warmup,
+        "timing": "geo_time_next_render event pairs on each kernel dispatch; blocks of n renders of the adaptive disk "
+                  "frame with the state off (geo_render_disk_adaptive), with it on (geo_render_disk_adaptive_ring), the "
+                  "plain adaptive frame and the plain adaptive GEO_FLAG_RING_F64 frame alternate in one process, each "
+                  "kind on its own context; spread = (max - min) / median of a kind's alternation medians; a cost is a "
+                  "figure only beyond twice its off side's spread",
+        "sessions": [adaptive_ring_session(args, cfg, frame, scenes, sky, tex) for _ in range(args.sessions)],
     }
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -9,7 +9,7 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
         [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
-        [--disk-ring-f64] [--adaptive [--tol T] [--ss]]
+        [--disk-ring-f64] [--adaptive [--tol T] [--ss | --disk-ring-f64]]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -30,7 +30,10 @@ accuracy bar), on the GPU or with --cpu, not with --ss.
 --adaptive draws the disk frame with the error-controlled integrator
 (GEO_MODE_ADAPTIVE through geo_render_disk_adaptive, --tol its tolerance in u,
 0 = the default 1e-6), unshaded, with --disk-shift or with --disk-emission, on
-the GPU or with --cpu; not with --disk-ring-f64.  With --ss the GPU frame goes
+the GPU or with --cpu.  With --disk-ring-f64 the frame goes through
+geo_render_disk_adaptive_ring (--cpu: geo_render_cpu_disk_adaptive_ring_f64):
+the capture band's pixels in f64, the rest by the adaptive integrator; not
+together with --ss.  With --ss the GPU frame goes
 through geo_render_disk_adaptive_batch with one frame (the only call that
 supersamples an adaptive disk frame), and --cpu renders
 geo_render_cpu_disk_adaptive at twice the size and box-resolves it here
@@ -96,16 +99,17 @@ def disk_frame(args):
                 u32, vp]
         ring = 1 if args.disk_ring_f64 else 0
         if args.adaptive:
-            name = "geo_render_cpu_disk_adaptive"
+            # (with ring = 0 the function is geo_render_cpu_disk_adaptive)
+            name = "geo_render_cpu_disk_adaptive_ring_f64"
             shift = None
             if args.disk_shift:
                 shift = _lib.GeoDiskShift(int(args.disk_shift[0]), int(args.disk_shift[1]), args.disk_shift[2])
-            lib.geo_render_cpu_disk_adaptive.restype = ctypes.c_int
-            lib.geo_render_cpu_disk_adaptive.argtypes = base + [vp, vp, u32, vp, vp, vp]
-            rc = lib.geo_render_cpu_disk_adaptive(
+            lib.geo_render_cpu_disk_adaptive_ring_f64.restype = ctypes.c_int
+            lib.geo_render_cpu_disk_adaptive_ring_f64.argtypes = base + [vp, vp, u32, vp, vp, vp, ctypes.c_int]
+            rc = lib.geo_render_cpu_disk_adaptive_ring_f64(
                 *common, ctypes.addressof(emission) if emission is not None else None,
                 ramp.ctypes.data if ramp is not None else None, ramp.shape[0] if ramp is not None else 0, None, None,
-                ctypes.addressof(shift) if shift else None)
+                ctypes.addressof(shift) if shift else None, ring)
         elif emission is not None:
             name = "geo_render_cpu_disk_ring_f64"
             lib.geo_render_cpu_disk_ring_f64.restype = ctypes.c_int
@@ -145,6 +149,8 @@ def disk_frame(args):
             rgba = torch.empty(nb * 8 * w * 4, dtype=torch.uint8, device="cuda:0")
             ctx.render_disk_adaptive_batch([frame], scene, w, h, 8, 0, 8, nb, rgba)
             rgba = rgba[:w * h * 4]
+        elif args.adaptive and args.disk_ring_f64:
+            ctx.render_disk_adaptive_ring(frame, scene, w, h, h, 0, h, 1, rgba)
         elif args.adaptive:
             ctx.render_disk_adaptive(frame, scene, w, h, h, 0, h, 1, rgba)
         else:
@@ -158,7 +164,8 @@ def disk_frame(args):
     else:
         imageio.save_png(args.out, rgba, w, h)
     print(f"wrote {args.out} ({w}x{h}{', 2x2 supersampled' if args.ss else ''}"
-          f"{', adaptive' if args.adaptive else ''}, thin disk {r_in}..{r_out}, "
+          f"{', adaptive' if args.adaptive else ''}{', f64 band' if args.disk_ring_f64 else ''}, "
+          f"thin disk {r_in}..{r_out}, "
           f"{'CPU path' if args.cpu else 'GPU'})")
 
 
@@ -190,7 +197,8 @@ def main():
                    help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); not with --ss")
     p.add_argument("--adaptive", action="store_true",
                    help="with --disk: the error-controlled integrator (geo_render_disk_adaptive; with --ss "
-                        "geo_render_disk_adaptive_batch with one frame); not with --disk-ring-f64")
+                        "geo_render_disk_adaptive_batch with one frame; with --disk-ring-f64 "
+                        "geo_render_disk_adaptive_ring)")
     p.add_argument("--tol", type=float, default=0.0, help="with --adaptive: the tolerance in u (0 = 1e-6)")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
@@ -200,8 +208,8 @@ def main():
     args = p.parse_args()
     if args.disk_ring_f64 and (not args.disk or args.ss):
         p.error("--disk-ring-f64 goes with --disk and without --ss (a supersampled disk frame refuses the state)")
-    if args.adaptive and (not args.disk or args.disk_ring_f64):
-        p.error("--adaptive goes with --disk and without --disk-ring-f64 (the adaptive disk has no f64 band)")
+    if args.adaptive and not args.disk:
+        p.error("--adaptive goes with --disk")
     if args.tol != 0.0 and not args.adaptive:
         p.error("--tol goes with --adaptive")
     if args.disk:
