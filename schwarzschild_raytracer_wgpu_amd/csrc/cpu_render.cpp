@@ -197,7 +197,7 @@ unsigned long long run_rows_disk(const CpuJob& j, unsigned tid, unsigned nthread
             uint32_t n = 0;
             if (j.dring) {
                 // geo_render_disk_ring_kernel per pixel
-                // (geo_render_disk_adaptive_ring_kernel with j.dadaptive): the
+                // (its GEO_MODE_ADAPTIVE with j.dadaptive): the
                 // band's lanes by the f64 path, the others as below, both
                 // through DiskHits
                 float lam;

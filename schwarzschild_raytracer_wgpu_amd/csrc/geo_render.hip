@@ -899,8 +899,8 @@ static DiskEmitArgs emit_args(const geo_ctx* c, const RenderCall& rc, const Rend
 // buffer armed; the disk's constants do not depend on the resolution), or
 // with geo_set_disk_ring_f64 on (geo_render_disk_ring_kernel:
 // the band's constants ride as a further argument; the curved kinds only, a
-// capture orbit needs rs > 0), or adaptive with it on
-// (geo_render_disk_adaptive_ring: geo_render_disk_adaptive_ring_kernel, the
+// capture orbit needs rs > 0), direct or adaptive
+// (geo_render_disk_adaptive_ring: the same kernel's GEO_MODE_ADAPTIVE, the
 // same arguments).  The rules let no adaptive SS4 frame through.
 static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskArgs d;
@@ -927,10 +927,9 @@ static int launch_disk_frame(const geo_ctx* c, const RenderCall& rc, const Rende
             if (w.disk_ring) {
                 if constexpr (KIND != geo::kFlat) {
                     // (adaptive: geo_render_disk_adaptive_ring alone; the rules refuse the older calls)
-                    if (w.adaptive)
-                        return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_adaptive_ring_kernel<KIND, SHADE>, fb, d,
-                                                  x, bk);
-                    return launch_wave_blocks(w.a, w.p, 1, geo_render_disk_ring_kernel<KIND, SHADE>, fb, d, x, bk);
+                    const auto direct = geo_render_disk_ring_kernel<KIND, SHADE, GEO_MODE_DIRECT>;
+                    const auto adaptive = geo_render_disk_ring_kernel<KIND, SHADE, GEO_MODE_ADAPTIVE>;
+                    return launch_wave_blocks(w.a, w.p, 1, w.adaptive ? adaptive : direct, fb, d, x, bk);
                 }
                 return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
             }

@@ -720,20 +720,35 @@ struct SsPitch<true> {
 // with the band's lanes (geo::in_band on the f32 ray, GEO_FLAG_RING_F64's
 // test) taken through the f64 path of geo_band.h, probes included
 // (geo::disk_hits_band).  Kernels with their own body on the same launch
-// geometry, not a property of wave_block_body below: their lanes go through
-// geo::DiskHits and geo::disk_shade_hits, which the three geo::disk_shade*
-// forms are not yet expressed through.  As in
-// geo_render_kernel<..., RING>, the band's constants are a kernel argument
-// copied to LDS, a wave's f32 lanes run their loop (geo::geodesic_angle_disk)
-// first and its band lanes, if it has any, the f64 loop in a cold arm, and a
-// band lane's steps count twice in its tile's cost.  Both kinds of lane hand
-// their crossings on as geo::DiskHits, and one shading follows.  rs > 0 and
+// geometry, not a property of wave_block_body below: the band's constants are a
+// kernel argument copied to LDS, as in geo_render_kernel<..., RING>, a wave's
+// f32 lanes run their loop first and its band lanes, if it has any, the f64
+// loop in a cold arm behind one ballot, and a band lane's steps count twice in
+// its tile's cost.  Both kinds of lane hand their crossings on as
+// geo::DiskHits, and one geo::disk_shade_hits follows (which the three
+// geo::disk_shade* forms of wave_block_body are not yet expressed through).  No thread returns
+// before the barrier except by the workgroup-uniform padding exit.  rs > 0 and
 // r_obs > rs (a capture orbit): the curved kinds only.
-template <int KIND, Shade SHADE>
+//   MODE   the f32 lanes' integrator: GEO_MODE_DIRECT (geo::disk_ray,
+//          geo::geodesic_angle_disk), or GEO_MODE_ADAPTIVE
+//          (geo_render_disk_adaptive_ring: geo::disk_ray_adaptive makes every
+//          lane's DiskRay, of which the band's f64 path reads only ak[0] and
+//          "no crossing", and geo::geodesic_angle_adaptive_disk; the band's
+//          lanes take the scene's step and max_steps as the f64 loop's fixed
+//          step and budget).  The step slots then mix units, as the plain
+//          adaptive GEO_FLAG_RING_F64 render's do: attempted adaptive steps of
+//          the f32 lanes, fixed f64 steps of the band's.  So does the tile
+//          cost: the wave's largest count of RK5(4) attempts (~57 VALU each;
+//          a.cost_overhead is the adaptive mode's, in attempts) plus twice its
+//          largest count of f64 RK4 steps, where the unit beside it in the
+//          direct mode is the cheaper f32 RK4 step.  The cost only orders the
+//          tiles of this render's own grid key.
+template <int KIND, Shade SHADE, int MODE>
 __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderArgs a, const FrameBatch<1> fb,
                                                                   const DiskArgs d, const ShadeFrameArg<SHADE> x,
                                                                   const BandArg<true> bk) {
     static_assert(KIND != geo::kFlat && SHADE != Shade::kSky, "no capture orbit without a black hole; a disk render");
+    static_assert(MODE == GEO_MODE_DIRECT || MODE == GEO_MODE_ADAPTIVE, "the f32 lanes' integrator");
     static_assert(kKernargsFit<RenderArgs, FrameBatch<1>, DiskArgs, ShadeFrameArg<SHADE>, BandArg<true>>);
     const FrameK& f = fb.f[0];
     const uint32_t L = blockIdx.x;
@@ -774,7 +789,10 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
         const float ct = geo::central_rho(c2x, c2y);
         const float rct = geo::rcpf_(ct);
         geo::DiskRay dr;
-        geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        if constexpr (MODE == GEO_MODE_ADAPTIVE)
+            geo::disk_ray_adaptive(d.k, a.k, c2x, c2y, ct, rct, &dr);
+        else
+            geo::disk_ray(d.k, a.k, c2x, c2y, ct, rct, &dr);
         f64_lane = geo::in_band(bkl.kx, ct);
         float lam = 0.0f;
         bool bh = false;
@@ -786,7 +804,11 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
         }
         if (!f64_lane) {
             float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+            float ang;
+            if constexpr (MODE == GEO_MODE_ADAPTIVE)
+                ang = geo::geodesic_angle_adaptive_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
+            else
+                ang = geo::geodesic_angle_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
             lam = geo::kPi2 - ang;
             bh = lam < geo::kBlackHoleLambda;
             geo::disk_hits_f32(d.k, a.k, dr, Uk, steps, ang, &h);
@@ -838,147 +860,6 @@ __global__ __launch_bounds__(64) void geo_render_disk_ring_kernel(const RenderAr
     // wave_block_body's epilogue with the ring kernel's tile cost: the wave runs its
     // f32 lanes' loop, then its band lanes' f64 loop at about twice the cost
     // per step (every lane of the wave is active again here)
-    if (a.step_slots) {
-        const uint32_t total = wave_sum_u32(steps);
-        const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
-        if (lane == 0 && total) atomicAdd(&a.step_slots[slot * kSlotStride], (unsigned long long)total);
-    }
-    if (a.tile_cost) {
-        const uint32_t wmax = wave_max_u32(f64_lane ? 0u : steps) + 2u * wave_max_u32(f64_lane ? steps : 0u);
-        if (lane == 0) atomicAdd(&a.tile_cost[tile.y * tiles_x + tile.x], wmax + a.cost_overhead);
-    }
-}
-
-// ---- geo_render_disk_adaptive_ring: the adaptive disk with the f64 band ----
-// geo_render_disk_ring_kernel with the adaptive integrator in its f32 lanes:
-// geo::disk_ray_adaptive makes every lane's DiskRay (the band's f64 path reads
-// only ak[0] and "no crossing" of it), the f32 lanes run
-// geo::geodesic_angle_adaptive_disk and hand their crossings on through
-// geo::disk_hits_f32, the band's lanes skip that loop and take
-// geo::disk_hits_band in the cold arm behind one ballot with the scene's step
-// and max_steps as the f64 loop's fixed step and budget, and one
-// geo::disk_shade_hits follows.  The body is restated, not shared: the direct
-// ring kernels above keep their instructions and registers that way (routed
-// through a shared body their shaded instantiations took 81 VGPRs, see
-// disk_ring_body below).  The same launch geometry, LDS copy and early exit:
-// no thread returns before the barrier except by the workgroup-uniform
-// padding exit.
-template <int KIND, Shade SHADE>
-__global__ __launch_bounds__(64) void geo_render_disk_adaptive_ring_kernel(const RenderArgs a, const FrameBatch<1> fb,
-                                                                           const DiskArgs d,
-                                                                           const ShadeFrameArg<SHADE> x,
-                                                                           const BandArg<true> bk) {
-    static_assert(KIND != geo::kFlat && SHADE != Shade::kSky, "no capture orbit without a black hole; a disk render");
-    static_assert(kKernargsFit<RenderArgs, FrameBatch<1>, DiskArgs, ShadeFrameArg<SHADE>, BandArg<true>>);
-    const FrameK& f = fb.f[0];
-    const uint32_t L = blockIdx.x;
-    const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
-    const uint32_t wave = (L >> 3) & 3u;
-    if (pos >= a.launch_tiles) return;  // the padding of the last group (a whole workgroup)
-    const uint32_t tiles_x = a.tiles_x;
-    uint2 tile;
-    if (a.tile_order) {
-        const uint32_t t = a.tile_order[pos];
-        tile = make_uint2(t & 0xFFFFu, t >> 16);
-    } else {
-        tile = make_uint2(pos % tiles_x, a.tile_y0 + pos / tiles_x);
-    }
-    const uint32_t lane = threadIdx.x & 63u;
-    // the band's constants in LDS: one 8-byte word per thread (kBandDwords / 2 <= 64)
-    __shared__ double band_lds[kBandDwords / 2u];
-    if (threadIdx.x < kBandDwords / 2u)
-        reinterpret_cast<uint2*>(band_lds)[threadIdx.x] = reinterpret_cast<const uint2*>(&bk.k)[threadIdx.x];
-    __syncthreads();
-    const geo::BandConsts& bkl = *reinterpret_cast<const geo::BandConsts*>(band_lds);
-    const uint32_t px = tile.x * kTileW + (wave % kWavesX) * kWaveW + lane % kWaveW;
-    const uint32_t wl0 = tile.y * kTileH + (wave / kWavesX) * kWaveRows;
-    const uint32_t ly = wl0 + lane / kWaveW;
-    const uint32_t band = __umulhi(wl0, a.band_magic);
-    const uint32_t py = a.row0 + band * a.band_stride + (wl0 - band * a.band_rows) + (ly - wl0);
-    uint32_t steps = 0;
-    bool f64_lane = false;
-    if (px < a.width && ly < a.nrows && py < a.height) {
-        float c2x, c2y, c2z, g_obs = 1.0f;
-        if constexpr (SHADE == Shade::kDisk)
-            geo::pixel_central_dir(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px,
-                                   py, &c2x, &c2y, &c2z);
-        else
-            geo::pixel_central_dir_g(f.cam, f.frame.movement_to_central, f.frame.psi_factor_and_position[0], f.kt, px,
-                                     py, &c2x, &c2y, &c2z, &g_obs);
-        const float st = geo::central_sin(c2z);
-        const float ct = geo::central_rho(c2x, c2y);
-        const float rct = geo::rcpf_(ct);
-        geo::DiskRay dr;
-        geo::disk_ray_adaptive(d.k, a.k, c2x, c2y, ct, rct, &dr);
-        f64_lane = geo::in_band(bkl.kx, ct);
-        float lam = 0.0f;
-        bool bh = false;
-        geo::DiskHits h;
-#pragma unroll
-        for (int c = 0; c < geo::kDiskMaxCrossings; ++c) {
-            h.hit[c] = false;
-            h.r[c] = 0.0f;
-        }
-        if (!f64_lane) {
-            float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_adaptive_disk<KIND>(a.k, st, ct, rct, dr, &steps, Uk);
-            lam = geo::kPi2 - ang;
-            bh = lam < geo::kBlackHoleLambda;
-            geo::disk_hits_f32(d.k, a.k, dr, Uk, steps, ang, &h);
-        }
-        if (geo::ballot_(f64_lane) != 0) {
-            if (f64_lane) {
-                GEO_COLD_ARM();
-                const double l = geo::disk_hits_band(bkl, d.k, dr, px, py, &steps, &h);
-                lam = (float)l;
-                bh = l < (double)geo::kBlackHoleLambda;
-            }
-        }
-        float U = 0.0f, V = 0.0f;
-        if (!bh || a.out_uv) geo::sky_uv(f.frame.central_to_uv, c2x, c2y, ct, rct, lam, &U, &V);
-        const size_t o = (size_t)ly * a.width + px;
-        const uint32_t base =
-            bh ? geo::kBlackRGBA : geo::sample_sky_qf(level0_quad(a), a.sky_w256, a.sky_h256, a.sky_opaque != 0, U, V);
-        const PaddedSkyQuad dquad{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(d.tex), 0, (int)d.tex_bytes,
-                                                                    kBufferRsrcWord3),
-                                  d.tex_pitch_b};
-        const auto dsample = [&](float Ud, float Vd) {
-            return geo::sample_sky_quad_f(dquad, d.tex_w256, d.tex_h256, Ud, Vd);
-        };
-        float* const hits = d.out_hits ? d.out_hits + o * (2u * geo::kDiskMaxCrossings) : nullptr;
-        if constexpr (SHADE == Shade::kDiskEmit) {
-            const DiskEmitArgs& em = x;
-            const auto rfetch = [ramp = em.ramp](uint32_t i) { return ramp[i]; };
-            geo::DiskShiftRay sr;
-            geo::disk_shift_ray(d.k, em.k.s, dr, ct, g_obs, &sr);
-            a.out_rgba[o] = geo::disk_shade_hits(d.k, dr, h, base,
-                                                 geo::disk_colour_emit(d.k, a.k, em.k, sr, dsample, rfetch), hits,
-                                                 em.out_g ? em.out_g + o * geo::kDiskMaxCrossings : nullptr,
-                                                 em.out_q ? em.out_q + o * geo::kDiskMaxCrossings : nullptr);
-        } else if constexpr (SHADE == Shade::kDiskShift) {
-            const DiskShiftArgs& sh = x;
-            geo::DiskShiftRay sr;
-            geo::disk_shift_ray(d.k, sh.k, dr, ct, g_obs, &sr);
-            a.out_rgba[o] = geo::disk_shade_hits(d.k, dr, h, base, geo::disk_colour_shift(a.k, sh.k, sr, dsample),
-                                                 hits, sh.out_g ? sh.out_g + o * geo::kDiskMaxCrossings : nullptr,
-                                                 nullptr);
-        } else {
-            a.out_rgba[o] = geo::disk_shade_hits(d.k, dr, h, base, geo::disk_colour_plain(dsample), hits, nullptr,
-                                                 nullptr);
-        }
-        if (a.out_mask) a.out_mask[o] = bh ? 1 : 0;
-        if (a.out_uv) a.out_uv[o] = make_float2(U, V);
-        if (a.out_steps) a.out_steps[o] = steps;
-    }
-    // geo_render_disk_ring_kernel's epilogue (every lane of the wave is active
-    // again here).  The step slots mix units, as the plain adaptive
-    // GEO_FLAG_RING_F64 render's do: attempted adaptive steps of the f32 lanes,
-    // fixed f64 steps of the band's.  So does the tile cost: the wave's largest
-    // count of RK5(4) attempts (~57 VALU each; a.cost_overhead is the adaptive
-    // mode's, in attempts) plus twice its largest count of f64 RK4 steps, a
-    // band lane's step counted twice as in the direct ring kernel, where the
-    // unit beside it is the cheaper f32 RK4 step.  The cost only orders the
-    // tiles of this render's own grid key.
     if (a.step_slots) {
         const uint32_t total = wave_sum_u32(steps);
         const uint32_t slot = (tile.x * (kBlock / 64) + wave) % kStepSlots;
@@ -1439,10 +1320,10 @@ __global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderA
 // band_words: the frame's geo::BandConsts as 8-byte words in the context's
 // device table (geo_band_table_kernel); every workgroup copies them to LDS, one
 // word per thread, behind the wave-uniform padding return and one barrier.
-// The one-frame kernel above keeps the body it has: routed through this one
-// (with DiskFrame as its source and its side outputs as a property) its shaded
-// instantiations came out with 81 VGPRs instead of 80, five waves per SIMD
-// instead of six.
+// The one-frame kernel above (geo_render_disk_ring_kernel, both of its modes)
+// keeps the body it has: routed through this one (with DiskFrame as its source
+// and its side outputs and its mode as properties) its shaded instantiations
+// came out with 81 VGPRs instead of 80, five waves per SIMD instead of six.
 template <int KIND, Shade SHADE, bool SS, typename SRC>
 __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& src, const uint2* band_words,
                                                uint32_t out_width) {
@@ -2050,12 +1931,12 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
     (void)geo_render_disk_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
     (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDisk>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDisk>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskShift>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit>;
-    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDisk, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDisk, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskShift, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_DIRECT>;
     (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, false>;
     (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, false>;
     (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false>;
@@ -2095,12 +1976,12 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_batch_kernel<geo::kFlat, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedOut, Shade::kDisk>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedIn, Shade::kDisk>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedOut, Shade::kDiskShift>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedIn, Shade::kDiskShift>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit>;
-    (void)geo_render_disk_adaptive_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDisk, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDisk, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
 }
 
 }  // namespace

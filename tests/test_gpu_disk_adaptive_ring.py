@@ -1,6 +1,6 @@
 """The adaptive disk with its capture band in f64 on the device
-(geo_render_disk_adaptive_ring, geo.h): the six
-geo_render_disk_adaptive_ring_kernel instantiations against the CPU path
+(geo_render_disk_adaptive_ring, geo.h): the six GEO_MODE_ADAPTIVE
+instantiations of geo_render_disk_ring_kernel against the CPU path
 (geo_render_cpu_disk_adaptive_ring_f64, the same headers) bit for bit in every
 output, the call's three properties on the device's own buffers, the band's
 hits, g and q against the independent f64 answer, fuzzed scenes, and the

@@ -1,5 +1,5 @@
 """The disk's capture band in f64 on the device (geo_set_disk_ring_f64):
-geo_render_disk_ring_kernel<KIND, SHADE> (unshaded, shifted, emission) against the CPU path
+geo_render_disk_ring_kernel<KIND, SHADE, GEO_MODE_DIRECT> (unshaded, shifted, emission) against the CPU path
 (geo_render_cpu_disk_ring_f64, the same headers csrc/geo_band.h and
 csrc/geo_disk.h) bit for bit in every output and the hit, g and q slots; the
 frame shapes and call forms; both dispatch orders; the state's rules and the

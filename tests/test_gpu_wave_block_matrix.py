@@ -7,10 +7,10 @@ with the CPU path of include/geo/geo_cpu.h.
   integration kind  kCurvedOut, kCurvedIn, kFlat
   shade             plain, shift (geo_set_disk_shift), emission (geo_set_disk_emission)
   form              frame direct / adaptive / SS4, batch direct / adaptive / SS4 / adaptive SS4
-  ring              geo_set_disk_ring_f64 on, the curved kinds: frame, batch, batch SS4
+  ring              geo_set_disk_ring_f64 on, the curved kinds: frame direct / adaptive, batch, batch SS4
   sky               GEO_FLAG_SS4 without a disk: frame, batch
 
-63 + 18 + 6 = 87 cells.  The other GPU tests compare these variants with the CPU
+63 + 24 + 6 = 93 cells.  The other GPU tests compare these variants with the CPU
 path on larger frames and more layouts; this one states that each instantiation
 is reached, so a launcher that names the wrong one fails in exactly its cells.
 
@@ -21,13 +21,21 @@ the gap keep their prefill.  An SS4 cell is the box resolve
 (test_ss_cpu.resolve) of the CPU path's one-sample render at 80 x 40 with the
 40 x 20 frame's uniform.  A ring cell has pixels (samples, under SS4) in the
 capture band (test_gpu_disk_ring_batch.in_band) and takes the band's lanes
-through geo_render_cpu_disk_ring_f64 / _shift_ring_f64 with the state on."""
+through geo_render_cpu_disk_ring_f64 / _shift_ring_f64 with the state on.  An
+adaptive ring frame is drawn through geo_render_disk_adaptive_ring on the same
+band set of 8 rows (the rules take it for that entry point as they do for
+geo_render_disk_adaptive) against test_disk_adaptive_ring_cpu.render, on the
+ring cells' own scenes (the ring walk's frame 0; kCurvedIn at step 1): its
+reference must differ from the adaptive state-off frame and from the direct
+ring cell's of the same kind and shade, so a launcher that names the other
+MODE fails in both of the pair's cells."""
 import math
 
 import numpy as np
 import pytest
 
 import test_disk_adaptive_cpu as A
+import test_disk_adaptive_ring_cpu as AR
 import test_disk_cpu as T
 import test_disk_ring_cpu as RC
 import test_gpu_disk_ring_batch as RB
@@ -53,7 +61,7 @@ SHADES = ("plain", "shift", "emission")
 FORMS = {"frame": (1, False, False), "frame_adaptive": (1, True, False), "frame_ss4": (1, False, True),
          "batch": (2, False, False), "batch_adaptive": (2, True, False), "batch_ss4": (2, False, True),
          "batch_adaptive_ss4": (2, True, True)}
-RING_FORMS = ("frame", "batch", "batch_ss4")
+RING_FORMS = ("frame", "frame_adaptive", "batch", "batch_ss4")
 SKY_FORMS = ("frame_ss4", "batch_ss4")
 
 # (kind, shade or "sky", form, ring)
@@ -64,7 +72,7 @@ IDS = [f"{k}-{s}-{'ring_' if r else ''}{f}" for k, s, f, r in CELLS]
 
 
 def test_the_matrix_has_a_cell_per_kernel():
-    assert len(CELLS) == 87 and len(set(IDS)) == 87
+    assert len(CELLS) == 93 and len(set(IDS)) == 93
 
 
 def cell_scenes(kind, n, ring):
@@ -100,7 +108,7 @@ def scene_as(s, adaptive=False, ss=False, disk=True):
 @pytest.fixture(scope="module")
 def cpu():
     lib = A.load_cpu()
-    ring = RC.load_cpu()
+    ring = AR.load_cpu()  # (test_disk_ring_cpu's library with the adaptive ring entry point)
     return lib, ring
 
 
@@ -118,6 +126,9 @@ def reference(cpu, kind, shade, adaptive, ss, ring, f):
         state = dict(shift=SHIFT if shade == "shift" else None, em=EM if shade == "emission" else None)
         if shade == "sky":
             rc, c = T.render(lib, frames[f], scene_as(scenes[f], disk=False), T.SKY, k * W, k * H)
+        elif adaptive and ring:
+            rc, c = AR.render(ring_lib, frames[f], scene_as(scenes[f], adaptive=True), T.make_disk(*disk), 1, k * W,
+                              k * H, **state)
         elif adaptive:
             rc, c = A.render(lib, frames[f], scene_as(scenes[f], adaptive=True), k * W, k * H, T.make_disk(*disk),
                              **state)
@@ -138,7 +149,13 @@ def reference(cpu, kind, shade, adaptive, ss, ring, f):
                 assert not np.array_equal(img, reference(cpu, kind, "plain", adaptive, ss, ring, f)), key
             if ring:
                 assert (RB.in_band(frames[f], scenes[f], k * W, k * H) & hit).sum() >= 1, key
-                rc, off = RC.render(ring_lib, frames[f], scenes[f], T.make_disk(*disk), 0, w=k * W, h=k * H, **state)
+                if adaptive:
+                    rc, off = A.render(lib, frames[f], scene_as(scenes[f], adaptive=True), k * W, k * H,
+                                       T.make_disk(*disk), **state)
+                    assert not np.array_equal(img, reference(cpu, kind, shade, False, ss, ring, f)), key
+                else:
+                    rc, off = RC.render(ring_lib, frames[f], scenes[f], T.make_disk(*disk), 0, w=k * W, h=k * H,
+                                        **state)
                 assert rc == GEO_OK and not np.array_equal(off["rgba"], c["rgba"]), key
     return _REFS[key]
 
@@ -164,7 +181,9 @@ def draw(dev, kind, shade, form, ring):
     stride = PACKED if n == 1 else STRIDE
     out = torch.full((n * stride,), FILL, dtype=torch.uint8, device=dev)
     if n == 1:
-        one = ctx.render_disk_adaptive if adaptive else ctx.render_band_set
+        one = ctx.render_disk_adaptive_ring if ring else ctx.render_disk_adaptive
+        if not adaptive:
+            one = ctx.render_band_set
         one(frames[0], scenes[0], W, H, BAND, 0, BAND, NB, out)
     else:
         if ring:
