@@ -71,7 +71,9 @@ extern "C" {
                                    announced by GEO_HAS_DISK_ADAPTIVE_BATCH:
                                    geo_render_disk_adaptive_batch;
                                    announced by GEO_HAS_DISK_ADAPTIVE_RING:
-                                   geo_render_disk_adaptive_ring) */
+                                   geo_render_disk_adaptive_ring;
+                                   announced by GEO_HAS_DISK_ADAPTIVE_RING_BATCH:
+                                   geo_render_disk_adaptive_ring_batch) */
 #define GEO_HAS_DISK 1
 #define GEO_HAS_DISK_SHIFT 1
 #define GEO_HAS_DISK_BATCH 1
@@ -84,6 +86,7 @@ extern "C" {
 #define GEO_HAS_DISK_ADAPTIVE 1
 #define GEO_HAS_DISK_ADAPTIVE_BATCH 1
 #define GEO_HAS_DISK_ADAPTIVE_RING 1
+#define GEO_HAS_DISK_ADAPTIVE_RING_BATCH 1
 
 typedef enum geo_status {
     GEO_OK = 0,
@@ -169,8 +172,9 @@ typedef enum geo_status {
                                    refuse the flag.  GEO_MODE_DIRECT (GEO_MODE_ADAPTIVE
                                    through geo_render_disk_adaptive, whose comment states
                                    the crossing rule of that mode,
-                                   geo_render_disk_adaptive_ring and
-                                   geo_render_disk_adaptive_batch alone),
+                                   geo_render_disk_adaptive_ring,
+                                   geo_render_disk_adaptive_batch and
+                                   geo_render_disk_adaptive_ring_batch alone),
                                    with GEO_FLAG_DEFER_STEPS at most; rs == 0, or r_obs > rs
                                    and rs < r_in; r_out < sphere_r and r_obs < sphere_r
                                    (GEO_EINVAL otherwise; GEO_ESTATE when no disk is set).
@@ -349,7 +353,9 @@ int geo_disk_hits_next_render(geo_ctx* ctx, float* out_hits);
  * geo_render_emission_batch (such a frame would come out without its band);
  * geo_render_disk_ring_batch (GEO_HAS_DISK_RING_BATCH) draws batched and
  * GEO_FLAG_SS4 disk frames with the band, and geo_render_disk_adaptive_ring
- * (GEO_HAS_DISK_ADAPTIVE_RING) one GEO_MODE_ADAPTIVE disk frame with it.
+ * (GEO_HAS_DISK_ADAPTIVE_RING) one GEO_MODE_ADAPTIVE disk frame with it, and
+ * geo_render_disk_adaptive_ring_batch (GEO_HAS_DISK_ADAPTIVE_RING_BATCH)
+ * batched and GEO_FLAG_SS4 GEO_MODE_ADAPTIVE disk frames.
  * Renders without GEO_FLAG_DISK are untouched, and GEO_FLAG_DISK |
  * GEO_FLAG_RING_F64 stays GEO_EINVAL everywhere.  Off by default; kept across
  * geo_set_disk, cleared by geo_clear_disk.  GEO_EINVAL for a NULL ctx. */
@@ -788,10 +794,10 @@ int geo_render_disk_adaptive(geo_ctx* ctx, const geo_frame* frame, const geo_sce
  * geo_set_dispatch (the learned order has a grid key of its own: the mode and
  * the band bit; a tile's cost is its waves' largest count of attempts plus
  * twice their largest count of f64 steps) and geo_set_tile_order work as for
- * geo_render_disk_adaptive.  Not in this ABI: batched frames and GEO_FLAG_SS4
- * with the adaptive band (an adaptive sibling of geo_render_disk_ring_batch)
- * and with it the multi-GPU pipeline's route for such a scene.  Every older
- * call keeps every refusal it has.  Asynchronous on `stream`. */
+ * geo_render_disk_adaptive.  Batched frames, GEO_FLAG_SS4 with the adaptive
+ * band and the multi-GPU pipeline's route for such a scene go through
+ * geo_render_disk_adaptive_ring_batch (this call keeps refusing the flag).
+ * Every older call keeps every refusal it has.  Asynchronous on `stream`. */
 int geo_render_disk_adaptive_ring(geo_ctx* ctx, const geo_frame* frame, const geo_scene* scene, uint32_t width,
                                   uint32_t height, uint32_t band_rows, uint32_t row0, uint32_t row_stride,
                                   uint32_t nbands, uint8_t* out_rgba8, uint8_t* out_mask, float* out_uv,
@@ -833,15 +839,70 @@ int geo_render_disk_adaptive_ring(geo_ctx* ctx, const geo_frame* frame, const ge
  * geo_set_tile_order work as for the other batches (frame 0 records the tile
  * costs, a tile's cost being in attempts; the learned order's key holds the
  * mode beside the disk, SS and emission bits; under GEO_FLAG_SS4 the grid is
- * the sample frame's).  Not in this ABI: per-pixel outputs from a batch, and
- * the f64 capture band in a batch of adaptive disk frames or under
- * GEO_FLAG_SS4 (geo_render_disk_adaptive_ring draws one one-sample frame with
- * it).  Every older call keeps every refusal it has.  One scene for every
- * frame: pass copies.  Asynchronous on `stream`. */
+ * the sample frame's).  Not in this ABI: per-pixel outputs from a batch.  The
+ * f64 capture band in a batch of adaptive disk frames or under GEO_FLAG_SS4
+ * goes through geo_render_disk_adaptive_ring_batch (this call keeps refusing
+ * that state).  Every older call keeps every refusal it has.  One scene for
+ * every frame: pass copies.  Asynchronous on `stream`. */
 int geo_render_disk_adaptive_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes, uint32_t nframes,
                                    uint32_t width, uint32_t height, uint32_t band_rows, uint32_t row0,
                                    uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8, size_t out_frame_stride,
                                    unsigned long long* steps_total, void* stream);
+
+/* geo_render_band_set_batch for the adaptive disk with its capture band in f64
+ * (GEO_HAS_DISK_ADAPTIVE_RING_BATCH): nframes (1 .. GEO_MAX_BATCH_FRAMES)
+ * GEO_MODE_ADAPTIVE | GEO_FLAG_DISK frames of a context with
+ * geo_set_disk_ring_f64 on, in ONE render launch, scenes[f] for frames[f], the
+ * band-set layout and the out_frame_stride rules of the other batches.  The
+ * shading is what the context has set: none, geo_set_disk_shift, or
+ * geo_set_disk_emission (which takes the shift's place, as everywhere else).
+ * One-sample frames: frame f's bytes are those of
+ * geo_render_disk_adaptive_ring with frames[f], scenes[f], the same layout and
+ * the same context state, bit for bit, and so
+ * geo_render_cpu_disk_adaptive_ring_f64's; steps_total (or the deferred
+ * accumulator) is the sum of those renders' counts, in their mixed units:
+ * adaptive attempts outside the band, fixed f64 steps inside it.
+ * GEO_FLAG_SS4 on every scene or on none (width, height, rows and bands are
+ * then in output pixels, with geo_render_ss_batch's size limits of 2^19).  No
+ * one-frame supersampled adaptive ring render exists
+ * (geo_render_disk_adaptive_ring keeps refusing the flag), so the flag's own
+ * definition fixes frame f: output pixel (x, y) is the per-channel
+ * (s00 + s01 + s10 + s11 + 2) >> 2 of pixels (2x + i, 2y + j) of the one-sample
+ * geo_render_disk_adaptive_ring render at 2 width x 2 height with the same
+ * uniform and scene; the steps are those of every sample over sample rows 2r,
+ * 2r + 1.
+ * Every scene carries GEO_MODE_ADAPTIVE and GEO_FLAG_DISK, with
+ * GEO_FLAG_DEFER_STEPS and GEO_FLAG_SS4 at most, and tol under the adaptive
+ * mode's rules; the scenes may differ in r_obs only (tol, step and the budget
+ * are equal across the batch; the band's lanes take step and max_steps as
+ * their f64 loop's fixed step and budget) and share the integration kind.
+ * GEO_EINVAL for GEO_MODE_DIRECT and GEO_MODE_FAN scenes (geo_render_disk_ring_batch
+ * draws the direct ones), for any other flag (GEO_FLAG_RING_F64, _MIPS and
+ * _COMPOSITE included), and wherever a rule of geo_render_disk_adaptive_batch
+ * is broken.  GEO_ESTATE with the ring state off (the call has nothing to draw
+ * that geo_render_disk_adaptive_batch does not), or without a sky or a disk.
+ * With rs == 0 there is no capture orbit: the state is ignored and the frames
+ * are geo_render_disk_adaptive_batch's, kernels and bytes.  Colour only: a
+ * buffer armed by geo_disk_hits_next_render, geo_disk_shift_next_render or
+ * geo_disk_emission_next_render is consumed and the call returns GEO_EINVAL.
+ * A refused call launches nothing, writes nothing and drops the timing pair;
+ * ctx, frames, scenes or out_rgba8 NULL and nframes out of range are refused
+ * before any device work.  geo_time_next_render (the render launch; a small
+ * kernel that writes the frames' band constants to a context-owned table runs
+ * on `stream` before it), geo_set_dispatch and geo_set_tile_order work as for
+ * the other batches (frame 0 records the tile costs, a tile's cost being its
+ * waves' largest count of attempts plus twice their largest count of f64
+ * steps; the learned order's key holds the mode and the band bit, so it
+ * differs from geo_render_disk_ring_batch's and from
+ * geo_render_disk_adaptive_batch's; under GEO_FLAG_SS4 the grid is the sample
+ * frame's).  Not in this ABI: per-pixel outputs from a batch.  Every older call
+ * keeps every refusal it has: geo_render_disk_adaptive_batch stays GEO_EINVAL
+ * with the state on and rs > 0, geo_render_disk_ring_batch for adaptive scenes.
+ * One scene for every frame: pass copies.  Asynchronous on `stream`. */
+int geo_render_disk_adaptive_ring_batch(geo_ctx* ctx, const geo_frame* frames, const geo_scene* scenes,
+                                        uint32_t nframes, uint32_t width, uint32_t height, uint32_t band_rows,
+                                        uint32_t row0, uint32_t row_stride, uint32_t nbands, uint8_t* out_rgba8,
+                                        size_t out_frame_stride, unsigned long long* steps_total, void* stream);
 
 /* Rank 0's reassembly for the LEAD layout (multi-GPU present with rank 0
  * taking a larger share: it renders but never sends its rows, while the peers'

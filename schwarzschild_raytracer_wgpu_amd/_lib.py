@@ -45,6 +45,7 @@ GEO_HAS_DISK_RING_BATCH = 1  # geo_render_disk_ring_batch
 GEO_HAS_DISK_ADAPTIVE = 1  # geo_render_disk_adaptive
 GEO_HAS_DISK_ADAPTIVE_BATCH = 1  # geo_render_disk_adaptive_batch
 GEO_HAS_DISK_ADAPTIVE_RING = 1  # geo_render_disk_adaptive_ring
+GEO_HAS_DISK_ADAPTIVE_RING_BATCH = 1  # geo_render_disk_adaptive_ring_batch
 GEO_DISK_PROFILE_POWER = 0
 GEO_DISK_PROFILE_THIN = 1
 GEO_DISK_RAMP_MAX = 1024
@@ -199,6 +200,11 @@ SIGNATURES = {
          _vp, _vp, _vp, _vp, _vp],
     ),
     "geo_render_disk_adaptive_batch": (
+        _int,
+        [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
+         ctypes.c_size_t, _vp, _vp],
+    ),
+    "geo_render_disk_adaptive_ring_batch": (
         _int,
         [_vp, ctypes.POINTER(GeoFrame), ctypes.POINTER(GeoScene), _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp,
          ctypes.c_size_t, _vp, _vp],

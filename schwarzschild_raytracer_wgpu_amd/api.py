@@ -433,6 +433,20 @@ class Context:
         self._render_batch("geo_render_disk_adaptive_batch", frames, scenes, width, height, band_rows, row0, row_stride,
                            nbands, out_rgba, frame_stride, steps_total, stream)
 
+    def render_disk_adaptive_ring_batch(self, frames, scenes, width: int, height: int, band_rows: int, row0: int,
+                                        row_stride: int, nbands: int, out_rgba, frame_stride: int | None = None,
+                                        steps_total=None, stream=None) -> None:
+        """geo_render_disk_adaptive_ring_batch: len(frames) (1 .. GEO_MAX_BATCH_FRAMES) GEO_MODE_ADAPTIVE |
+        GEO_FLAG_DISK frames of a context with set_disk_ring_f64 on (the capture band's pixels in f64;
+        GEO_ESTATE otherwise; rs == 0 ignores it) in one render launch, unshaded, shaded by set_disk_shift or
+        with set_disk_emission, with GEO_FLAG_SS4 on every scene or on none (sizes, rows and bands are then in
+        output pixels); frame f's packed bands at byte f*frame_stride of out_rgba (default: packed back to
+        back).  scenes: one GeoScene for every frame, or one per frame (a moving observer: they may differ in
+        r_obs only).  A one-sample frame is render_disk_adaptive_ring's bit for bit; steps_total mixes adaptive
+        attempts and the band's fixed f64 steps.  Colour only."""
+        self._render_batch("geo_render_disk_adaptive_ring_batch", frames, scenes, width, height, band_rows, row0,
+                           row_stride, nbands, out_rgba, frame_stride, steps_total, stream)
+
 
 def _batch_frames(frames, width: int, band_rows: int, nbands: int, out_rgba, frame_stride, steps_total, scenes=None):
     """The checks every batched render shares; (the frame count, the frames and the scenes (one GeoScene for

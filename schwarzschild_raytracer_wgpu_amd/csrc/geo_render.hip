@@ -809,9 +809,9 @@ static int choose_order(geo_ctx* c, const RenderCall& rc, RenderWork& w) {
     // emission render has a key of its own, as the disk render has, and a
     // disk render with geo_set_disk_ring_f64 on, for its band's tiles, one
     // frame or geo_render_disk_ring_batch's, whose frame 0 records them;
-    // geo_render_disk_adaptive_ring shares a key with neither the adaptive
-    // disk render, which has no disk_ring bit, nor the direct ring render,
-    // whose mode differs)
+    // geo_render_disk_adaptive_ring and geo_render_disk_adaptive_ring_batch
+    // share a key with neither the adaptive disk renders, which have no
+    // disk_ring bit, nor the direct ring renders, whose mode differs)
     const uint32_t key[9] = {rc.width, rc.height, rc.row0, rc.nrows, rc.band_rows, rc.band_stride, rc.scene->mode,
                              (w.mips ? 1u : 0u) | (w.ring ? 2u : 0u) | (w.disk ? 4u : 0u) | (w.ss ? 8u : 0u) |
                                  (w.emit ? 16u : 0u) | (w.disk_ring ? 32u : 0u),
@@ -1035,17 +1035,19 @@ static int fill_disk_batch(const geo_ctx* c, const RenderCall& rc, const RenderW
 
 // Stage 5, a batch of GEO_FLAG_DISK frames (geo_render_disk_batch,
 // geo_render_ss_batch's disk frames, geo_render_emission_batch,
-// geo_render_disk_adaptive_batch, and geo_render_disk_ring_batch with or without
-// a capture orbit to draw): geo_render_disk_batch_kernel with the frames in
+// geo_render_disk_adaptive_batch, and geo_render_disk_ring_batch and
+// geo_render_disk_adaptive_ring_batch with or without a capture orbit to
+// draw): geo_render_disk_batch_kernel with the frames in
 // grid.z, on the one-frame disk render's wave-block grid, not the plain batch's
 // 32 x 8-pixel workgroups: a disk wave holds more registers than a plain one,
 // and its frames are compared with one-frame launches wave for wave.
-// With a capture orbit, the ring kernels: each frame's band constants come from
+// With a capture orbit, the ring kernels, in the scenes' mode: each frame's
+// band constants come from
 // the one-frame launch's geo::band_consts (launch_disk_frame), at the sample
 // frame's size under GEO_FLAG_SS4, and reach the kernel through the device table
 // of the call's render-stream slot (geo_ctx::band_table), written on the call's
 // stream by geo_band_table_kernel just before the render launch: no host copy,
-// no wait.  The rules let no adaptive ring batch through.
+// no wait.
 static int launch_disk_frames(geo_ctx* c, const RenderCall& rc, const RenderWork& w) {
     DiskBatchArgs db;
     DiskEmitBatchArgs eb;
@@ -1077,14 +1079,16 @@ static int launch_disk_frames(geo_ctx* c, const RenderCall& rc, const RenderWork
                 constexpr bool SS = decltype(ss)::value;
                 SsPitch<SS> o;
                 if constexpr (SS) o.out_width = rc.width;
-                if (w.disk_ring) {
-                    if constexpr (KIND != geo::kFlat)
-                        return launch_wave_blocks(w.a, w.p, rc.nframes,
-                                                  geo_render_disk_ring_batch_kernel<KIND, SHADE, SS>, db, bands, x, o);
-                    return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
-                }
                 return with_flag(w.adaptive, [&](auto adaptive) {
                     constexpr int MODE = decltype(adaptive)::value ? GEO_MODE_ADAPTIVE : GEO_MODE_DIRECT;
+                    if (w.disk_ring) {
+                        // (adaptive: geo_render_disk_adaptive_ring_batch alone; the rules refuse the older calls)
+                        if constexpr (KIND != geo::kFlat)
+                            return launch_wave_blocks(w.a, w.p, rc.nframes,
+                                                      geo_render_disk_ring_batch_kernel<KIND, SHADE, SS, MODE>, db,
+                                                      bands, x, o);
+                        return (int)GEO_EINVAL;  // (never reached: the state is ignored for rs = 0)
+                    }
                     return launch_wave_blocks(w.a, w.p, rc.nframes, geo_render_disk_batch_kernel<KIND, SHADE, SS, MODE>,
                                               db, x, o);
                 });
@@ -1468,6 +1472,7 @@ GEO_BATCH_ENTRY(geo_render_ss_batch, Entry::kSsBatch)
 GEO_BATCH_ENTRY(geo_render_emission_batch, Entry::kEmissionBatch)
 GEO_BATCH_ENTRY(geo_render_disk_ring_batch, Entry::kDiskRingBatch)
 GEO_BATCH_ENTRY(geo_render_disk_adaptive_batch, Entry::kDiskAdaptiveBatch)
+GEO_BATCH_ENTRY(geo_render_disk_adaptive_ring_batch, Entry::kDiskAdaptiveRingBatch)
 #undef GEO_BATCH_ENTRY
 
 }  // extern "C"

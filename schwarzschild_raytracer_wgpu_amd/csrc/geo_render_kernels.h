@@ -731,7 +731,8 @@ struct SsPitch<true> {
 // r_obs > rs (a capture orbit): the curved kinds only.
 //   MODE   the f32 lanes' integrator: GEO_MODE_DIRECT (geo::disk_ray,
 //          geo::geodesic_angle_disk), or GEO_MODE_ADAPTIVE
-//          (geo_render_disk_adaptive_ring: geo::disk_ray_adaptive makes every
+//          (geo_render_disk_adaptive_ring, and disk_ring_body's frames of
+//          geo_render_disk_adaptive_ring_batch: geo::disk_ray_adaptive makes every
 //          lane's DiskRay, of which the band's f64 path reads only ak[0] and
 //          "no crossing", and geo::geodesic_angle_adaptive_disk; the band's
 //          lanes take the scene's step and max_steps as the f64 loop's fixed
@@ -1308,12 +1309,15 @@ __global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderA
 }
 
 // ---- the one body of the batched disk kernels with the f64 band -----------
-// geo_render_disk_ring_kernel's lanes (f32 lanes through
-// geo::geodesic_angle_disk and geo::disk_hits_f32, band lanes through
-// geo::disk_hits_band in a cold arm behind one ballot, then one
-// geo::disk_shade_hits) with wave_block_body's frame source, colour-only
-// output and SS4 resolve.  It varies along
+// geo_render_disk_ring_kernel's lanes (f32 lanes through MODE's integrator and
+// geo::disk_hits_f32, band lanes through geo::disk_hits_band in a cold arm
+// behind one ballot, then one geo::disk_shade_hits) with wave_block_body's
+// frame source, colour-only output and SS4 resolve.  It varies along
 //   SHADE  the shading: Shade::kDisk, kDiskShift, kDiskEmit
+//   MODE   the f32 lanes' integrator, as geo_render_disk_ring_kernel's MODE
+//          (there: what the band reads of an adaptive DiskRay, the band's step
+//          and budget, and the units the step slots and the tile cost then
+//          mix); GEO_MODE_ADAPTIVE: geo_render_disk_adaptive_ring_batch
 //   SS     GEO_FLAG_SS4, as in wave_block_body (the band's constants are then
 //          the sample frame's, and px, py the sample's)
 //   SRC    the frame source (DiskBatchFrame)
@@ -1324,10 +1328,11 @@ __global__ __launch_bounds__(64) void geo_render_disk_batch_kernel(const RenderA
 // keeps the body it has: routed through this one (with DiskFrame as its source
 // and its side outputs and its mode as properties) its shaded instantiations
 // came out with 81 VGPRs instead of 80, five waves per SIMD instead of six.
-template <int KIND, Shade SHADE, bool SS, typename SRC>
+template <int KIND, Shade SHADE, bool SS, int MODE, typename SRC>
 __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& src, const uint2* band_words,
                                                uint32_t out_width) {
     static_assert(KIND != geo::kFlat && SHADE != Shade::kSky, "no capture orbit without a black hole; a disk render");
+    static_assert(MODE == GEO_MODE_DIRECT || MODE == GEO_MODE_ADAPTIVE, "the f32 lanes' integrator");
     const uint32_t L = blockIdx.x;
     const uint32_t pos = ((L >> 5) << 3) + (L & 7u);
     const uint32_t wave = (L >> 3) & 3u;
@@ -1368,7 +1373,10 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
         const geo::PixelConsts& k = src.consts();
         const auto& dk = src.disk();
         geo::DiskRay dr;
-        geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
+        if constexpr (MODE == GEO_MODE_ADAPTIVE)
+            geo::disk_ray_adaptive(dk, k, c2x, c2y, ct, rct, &dr);
+        else
+            geo::disk_ray(dk, k, c2x, c2y, ct, rct, &dr);
         f64_lane = geo::in_band(bkl.kx, ct);
         float lam = 0.0f;
         bool bh = false;
@@ -1380,7 +1388,11 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
         }
         if (!f64_lane) {
             float Uk[geo::kDiskMaxCrossings];
-            const float ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            float ang;
+            if constexpr (MODE == GEO_MODE_ADAPTIVE)
+                ang = geo::geodesic_angle_adaptive_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
+            else
+                ang = geo::geodesic_angle_disk<KIND>(k, st, ct, rct, dr, &steps, Uk);
             lam = geo::kPi2 - ang;
             bh = lam < geo::kBlackHoleLambda;
             geo::disk_hits_f32(dk, k, dr, Uk, steps, ang, &h);
@@ -1446,7 +1458,8 @@ __device__ __forceinline__ void disk_ring_body(const RenderArgs& a, const SRC& s
 // ---- geo_render_disk_ring_batch: up to kMaxBatchFrames ring frames in one launch --
 // The disk batch, the SS batch's disk frames and the emission batch (SHADE) with
 // the band's lanes in f64: disk_ring_body on DiskBatchFrame, the frame in
-// blockIdx.z.  The argument segment has no room for eight frames'
+// blockIdx.z.  MODE: GEO_MODE_DIRECT, or the adaptive disk batch's frames
+// likewise (geo_render_disk_adaptive_ring_batch: GEO_MODE_ADAPTIVE).  The argument segment has no room for eight frames'
 // geo::BandConsts (8 x 344 bytes beside DiskBatchArgs' 3312), nor for the
 // display_to_movement rows they are derived from, so the host computes them
 // with the one-frame launch's geo::band_consts (at twice the size under SS4) and
@@ -1466,12 +1479,12 @@ __global__ __launch_bounds__(64) void geo_band_table_kernel(const BandTable t, g
 
 // bands: the table, frame z's constants at bands[z]; eb: the emission's
 // batch-uniform argument.
-template <int KIND, Shade SHADE, bool SS>
+template <int KIND, Shade SHADE, bool SS, int MODE>
 __device__ __forceinline__ void disk_ring_batch(const RenderArgs& a, const DiskBatchArgs& db,
                                                 const geo::BandConsts* bands, const ShadeBatchArg<SHADE>& eb,
                                                 uint32_t out_width) {
     static_assert(kKernargsFit<RenderArgs, DiskBatchArgs, const geo::BandConsts*, ShadeBatchArg<SHADE>, SsPitch<SS>>);
-    disk_ring_body<KIND, SHADE, SS>(a, DiskBatchFrame<ShadeBatchArg<SHADE>>{a, db, eb, blockIdx.z},
+    disk_ring_body<KIND, SHADE, SS, MODE>(a, DiskBatchFrame<ShadeBatchArg<SHADE>>{a, db, eb, blockIdx.z},
                                     reinterpret_cast<const uint2*>(bands + blockIdx.z), out_width);
 }
 
@@ -1482,12 +1495,15 @@ __device__ __forceinline__ void disk_ring_batch(const RenderArgs& a, const DiskB
 // holds more scalars (106) than the one-frame kernel (100).  With the target
 // they take 80, the others are unchanged, and none uses scratch;
 // profiles/disk_ring_batch_isa.txt.  The GEO_FLAG_SS4 instantiations, a lane
-// per sample of the 2W x 2H ring render, have no target: 0.)
-template <int KIND, Shade SHADE, bool SS>
+// per sample of the 2W x 2H ring render, have no target: 0.  The
+// GEO_MODE_ADAPTIVE instantiations came out in the class with the same
+// targets, 76 / 80 / 80 VGPRs one sample and SS4 alike, no scratch;
+// profiles/disk_adaptive_ring_batch_isa.txt.)
+template <int KIND, Shade SHADE, bool SS, int MODE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SS ? 0 : 6))) void geo_render_disk_ring_batch_kernel(
     const RenderArgs a, const DiskBatchArgs db, const geo::BandConsts* bands, const ShadeBatchArg<SHADE> eb,
     const SsPitch<SS> o) {
-    disk_ring_batch<KIND, SHADE, SS>(a, db, bands, eb, o.width());
+    disk_ring_batch<KIND, SHADE, SS, MODE>(a, db, bands, eb, o.width());
 }
 
 
@@ -1937,18 +1953,18 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_DIRECT>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_DIRECT>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_DIRECT>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, true>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, true>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true>;
-    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true, GEO_MODE_DIRECT>;
     (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_frame_kernel<geo::kCurvedOut, Shade::kDisk, GEO_MODE_ADAPTIVE>;
@@ -1982,6 +1998,18 @@ __global__ void geo_fan_kernel(double sphere_r, double schwarz_r, uint32_t max_i
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskShift, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedOut, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
     (void)geo_render_disk_ring_kernel<geo::kCurvedIn, Shade::kDiskEmit, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, false, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDisk, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskShift, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskShift, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedOut, Shade::kDiskEmit, true, GEO_MODE_ADAPTIVE>;
+    (void)geo_render_disk_ring_batch_kernel<geo::kCurvedIn, Shade::kDiskEmit, true, GEO_MODE_ADAPTIVE>;
 }
 
 }  // namespace

@@ -38,8 +38,14 @@ enum class Entry : uint8_t {
     kDiskRingBatch,      // geo_render_disk_ring_batch
     kDiskAdaptiveBatch,  // geo_render_disk_adaptive_batch
     kDiskAdaptiveRing,   // geo_render_disk_adaptive_ring
+    kDiskAdaptiveRingBatch,  // geo_render_disk_adaptive_ring_batch
 };
+// kEntries: the entries up to geo_render_disk_adaptive_ring.  That entry's host
+// driver (tests/native/render_rules_adaptive_ring_host.cpp) asserts the value,
+// so it stays; an entry appended after it counts in kEntryRows, the rows of
+// the traits table.
 constexpr int kEntries = 12;
+constexpr int kEntryRows = 13;
 
 enum class Ss : uint8_t { kNo, kOneFrame, kAnyFrames };  // GEO_FLAG_SS4: refused, drawn alone, drawn in any batch
 enum class Needs : uint8_t { kAnyScene, kDiskScene, kSsScene };
@@ -61,7 +67,7 @@ struct EntryTraits {
     bool colour_only;  // an armed per-pixel buffer refuses the call
     bool scene_per_frame;  // `scene` points at nframes scenes (they may differ in r_obs only)
 };
-constexpr EntryTraits kEntryTraits[kEntries] = {
+constexpr EntryTraits kEntryTraits[kEntryRows] = {
     // disk, mode, ss, scene, state, emission, band, colour_only, scene_per_frame; in Entry's order
     {true, GEO_MODE_DIRECT, Ss::kOneFrame, Needs::kAnyScene, NeedsState::kNone, true, Band::kOneSample, false, false},
     {true, GEO_MODE_DIRECT, Ss::kOneFrame, Needs::kAnyScene, NeedsState::kNone, true, Band::kOneSample, false, false},
@@ -75,7 +81,9 @@ constexpr EntryTraits kEntryTraits[kEntries] = {
     {true, GEO_MODE_DIRECT, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kRing, true, Band::kAll, true, true},
     {true, GEO_MODE_ADAPTIVE, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kNone, true, Band::kNoOrbit, true, true},
     {true, GEO_MODE_ADAPTIVE, Ss::kNo, Needs::kDiskScene, NeedsState::kRing, true, Band::kAll, false, false},
+    {true, GEO_MODE_ADAPTIVE, Ss::kAnyFrames, Needs::kDiskScene, NeedsState::kRing, true, Band::kAll, true, true},
 };
+static_assert((int)Entry::kDiskAdaptiveRingBatch + 1 == kEntryRows, "a row per entry");
 constexpr const EntryTraits& traits(Entry e) { return kEntryTraits[(int)e]; }
 
 // What the rules read of the context (geo_render.hip fills it in one place).
@@ -222,10 +230,10 @@ static inline int check_scene(const RuleState& c, const RenderCall& rc, RenderRu
     if ((scene->flags & ~(GEO_FLAG_DEFER_STEPS | GEO_FLAG_COMPOSITE | GEO_FLAG_MIPS | GEO_FLAG_RING_F64 |
                           GEO_FLAG_DISK | GEO_FLAG_SS4)) != 0)
         return GEO_RULE(13), GEO_EINVAL;
-    // geo_render_disk_adaptive, geo_render_disk_adaptive_ring and
-    // geo_render_disk_adaptive_batch draw GEO_MODE_ADAPTIVE disk scenes only,
-    // DISK with DEFER_STEPS (and SS4, the batch) at most (the older calls draw
-    // the direct and fan scenes)
+    // geo_render_disk_adaptive, geo_render_disk_adaptive_ring,
+    // geo_render_disk_adaptive_batch and geo_render_disk_adaptive_ring_batch
+    // draw GEO_MODE_ADAPTIVE disk scenes only, DISK with DEFER_STEPS (and SS4,
+    // the batches) at most (the older calls draw the direct and fan scenes)
     if (t.mode == GEO_MODE_ADAPTIVE &&
         (scene->mode != GEO_MODE_ADAPTIVE ||
          (scene->flags & ~(GEO_FLAG_DEFER_STEPS | (t.ss == Ss::kNo ? 0u : GEO_FLAG_SS4))) != GEO_FLAG_DISK))
@@ -326,7 +334,8 @@ static inline int check_frames(const RenderCall& rc, RenderRules& w, geo::PixelC
         // GEO_FLAG_DISK's rules for this frame's observer (frame 0's in check_scene)
         if (w.disk && i > 0 && (!(si.rs == 0.0f || si.r_obs > si.rs) || !(si.r_obs < si.sphere_r)))
             return GEO_RULE(38), GEO_EINVAL;
-        // geo_set_disk_ring_f64 in a batch (geo_render_disk_ring_batch): the
+        // geo_set_disk_ring_f64 in a batch (geo_render_disk_ring_batch,
+        // geo_render_disk_adaptive_ring_batch): the
         // frames share rs and each has passed the rule above, so frame 0's
         // w.disk_ring (rs > 0 and r_obs > rs: a capture orbit to draw) holds
         // for every frame; each gets band constants of its own (launch_ring_frames)
@@ -350,6 +359,9 @@ enum class Launcher : uint8_t {
 static inline Launcher choose_launcher(const RenderCall& rc, const RenderRules& w) {
     switch (rc.entry) {
         case Entry::kDiskAdaptiveBatch: return Launcher::kAdaptiveFrames;
+        case Entry::kDiskAdaptiveRingBatch:
+            // (no capture orbit, rs = 0: the state is ignored, geo_render_disk_adaptive_batch's kernels)
+            return w.disk_ring ? Launcher::kRingFrames : Launcher::kAdaptiveFrames;
         case Entry::kDiskRingBatch:
             // (no capture orbit, rs = 0: the state is ignored, the older batches' kernels)
             if (w.disk_ring) return Launcher::kRingFrames;

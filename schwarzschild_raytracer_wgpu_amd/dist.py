@@ -185,34 +185,46 @@ def _adaptive_disk(scene) -> bool:
     return scene.mode == GEO_MODE_ADAPTIVE and bool(scene.flags & GEO_FLAG_DISK)
 
 
-def _refuse_adaptive_ring(scene, ring_f64: bool) -> None:
-    """No call draws the adaptive disk's f64 band: refused by name, not by the launch's GEO_EINVAL."""
-    if scene.rs > 0 and ring_f64:
-        raise ValueError("a GEO_MODE_ADAPTIVE disk scene cannot be drawn with set_disk_ring_f64 on: "
-                         "geo_render_disk_adaptive and geo_render_disk_adaptive_batch draw no f64 band; use "
-                         "set_disk_ring_f64(False), or GEO_MODE_DIRECT")
+def _adaptive_ring(scene, ring_f64: bool, disk_ring_any_mode: bool) -> bool:
+    """Whether an adaptive disk scene is drawn with its f64 band (a capture orbit to draw, the state on, and
+    ShardedFrame's keyword); without the keyword such a scene is refused by name, not by the launch's
+    GEO_EINVAL."""
+    if not (scene.rs > 0 and ring_f64):
+        return False
+    if not disk_ring_any_mode:
+        raise ValueError("a GEO_MODE_ADAPTIVE disk scene cannot be drawn with set_disk_ring_f64 on through "
+                         "geo_render_disk_adaptive and geo_render_disk_adaptive_batch, which draw no f64 band: "
+                         "pass disk_ring_any_mode=True (geo_render_disk_adaptive_ring, "
+                         "geo_render_disk_adaptive_ring_batch), or use set_disk_ring_f64(False), or GEO_MODE_DIRECT")
+    return True
 
 
-def frame_entry(scene, ring_f64: bool) -> str:
+def frame_entry(scene, ring_f64: bool, disk_ring_any_mode: bool = False) -> str:
     """The library function that draws `scene` one frame at a time: geo_render_band_set, or for the adaptive
     disk geo_render_disk_adaptive (with GEO_FLAG_SS4, which has no one-frame call, the batched one with one
-    frame).  ring_f64: the context's set_disk_ring_f64 state."""
+    frame).  ring_f64: the context's set_disk_ring_f64 state; disk_ring_any_mode: ShardedFrame's keyword, with
+    which the adaptive disk in that state (rs > 0) goes to geo_render_disk_adaptive_ring, or to
+    geo_render_disk_adaptive_ring_batch with GEO_FLAG_SS4, and without which it is refused."""
     from ._lib import GEO_FLAG_SS4
 
     if not _adaptive_disk(scene):
         return "geo_render_band_set"
-    _refuse_adaptive_ring(scene, ring_f64)
+    if _adaptive_ring(scene, ring_f64, disk_ring_any_mode):
+        return "geo_render_disk_adaptive_ring_batch" if scene.flags & GEO_FLAG_SS4 else "geo_render_disk_adaptive_ring"
     return "geo_render_disk_adaptive_batch" if scene.flags & GEO_FLAG_SS4 else "geo_render_disk_adaptive"
 
 
-def batch_entry(scene, emission_set: bool, ring_f64: bool, emission_batch: bool, disk_ring_batch: bool) -> str:
+def batch_entry(scene, emission_set: bool, ring_f64: bool, emission_batch: bool, disk_ring_batch: bool,
+                disk_ring_any_mode: bool = False) -> str:
     """The library function that draws a batch of `scene`'s frames in one launch.  emission_set, ring_f64: the
-    context's states; emission_batch, disk_ring_batch: ShardedFrame's keywords, without which a disk scene in
-    that state is refused here, by name, as the older batched entry points refuse it with GEO_EINVAL."""
+    context's states; emission_batch, disk_ring_batch, disk_ring_any_mode: ShardedFrame's keywords, without
+    which a disk scene in that state is refused here, by name, as the older batched entry points refuse it with
+    GEO_EINVAL."""
     from ._lib import GEO_FLAG_DISK, GEO_FLAG_SS4
 
-    if _adaptive_disk(scene):  # (with GEO_FLAG_SS4 or without, any shading, no keyword)
-        _refuse_adaptive_ring(scene, ring_f64)
+    if _adaptive_disk(scene):  # (with GEO_FLAG_SS4 or without, any shading; no keyword with the ring state off)
+        if _adaptive_ring(scene, ring_f64, disk_ring_any_mode):
+            return "geo_render_disk_adaptive_ring_batch"
         return "geo_render_disk_adaptive_batch"
     disk = bool(scene.flags & GEO_FLAG_DISK)
     if disk and ring_f64:  # (with GEO_FLAG_SS4 or without, any shading: emission_batch is not needed)
@@ -271,7 +283,7 @@ class ShardedFrame:
     def __init__(self, ctx, frame, scene, width: int, height: int, band_rows: int, rank: int, world: int, device,
                  dist=None, host_gather: bool = False, frames_per_gather: int = 1, render_streams: int = 1,
                  present_rgb: bool = True, lead: int = 1, batch_launch: bool = False, peer_bands: int = 1,
-                 emission_batch: bool = False, disk_ring_batch: bool = False):
+                 emission_batch: bool = False, disk_ring_batch: bool = False, disk_ring_any_mode: bool = False):
         """host_gather: stage through host memory (gloo backend; rehearsals only).
         present_rgb: peers send RGB24 (geo_pack_rgb after each render; 25 %
         fewer bytes on the links) when the width is a multiple of 4.
@@ -298,7 +310,14 @@ class ShardedFrame:
         geo_render_disk_adaptive_batch with batch_launch (with GEO_FLAG_SS4 or
         without, any shading) and to geo_render_disk_adaptive without (a
         supersampled one through the batched call with one frame); while
-        set_disk_ring_f64 is on and rs > 0 it is refused (ValueError)."""
+        set_disk_ring_f64 is on and rs > 0 it is refused (ValueError) without
+        disk_ring_any_mode.
+        disk_ring_any_mode: such a scene in that state goes to
+        geo_render_disk_adaptive_ring_batch with batch_launch (with
+        GEO_FLAG_SS4 or without, any shading) and to
+        geo_render_disk_adaptive_ring without (a supersampled one through
+        the batched call with one frame).  Every other scene routes as
+        without it."""
         import torch
 
         from ._lib import lib
@@ -319,6 +338,7 @@ class ShardedFrame:
         self.batch = bool(batch_launch) and self.K > 1
         self.emission_batch = bool(emission_batch)
         self.disk_ring_batch = bool(disk_ring_batch)
+        self.disk_ring_any_mode = bool(disk_ring_any_mode)
         if self.batch and self.K > GEO_MAX_BATCH_FRAMES:
             raise ValueError(f"batch_launch: at most {GEO_MAX_BATCH_FRAMES} frames per gather")
         from ._lib import GEO_MODE_ADAPTIVE
@@ -327,7 +347,7 @@ class ShardedFrame:
         if self.batch:  # (a scene its path cannot draw is refused here, by name)
             self._batch_entry(scene)
         else:
-            frame_entry(scene, self._ring_f64())
+            self._frame_entry(scene)
         self.pending_frames = []     # batch mode: copies of the open batch's uniforms not yet rendered,
         self.pending_scenes = []     # and copies of their scenes (they differ in r_obs at most)
         self._pending_key = b""
@@ -399,8 +419,10 @@ class ShardedFrame:
             return
         sc = self.scene if scene is None else scene
         # (a supersampled adaptive disk scene has no one-frame call with these outputs: the library refuses it)
-        adaptive = frame_entry(sc, self._ring_f64()) != "geo_render_band_set"
-        render = self.ctx.render_disk_adaptive if adaptive else self.ctx.render_band_set
+        name = self._frame_entry(sc)
+        render = {"geo_render_band_set": self.ctx.render_band_set,
+                  "geo_render_disk_adaptive_ring": self.ctx.render_disk_adaptive_ring}.get(
+                      name, self.ctx.render_disk_adaptive)
         render(self.frame if frame is None else frame, sc, self.width, self.height, L.band_height(), L.row0(),
                L.cycle_rows, L.nbands(), buf, **outs)
 
@@ -418,9 +440,12 @@ class ShardedFrame:
     def _ring_f64(self) -> bool:
         return getattr(self.ctx, "disk_ring_f64", False)
 
+    def _frame_entry(self, scene) -> str:
+        return frame_entry(scene, self._ring_f64(), self.disk_ring_any_mode)
+
     def _batch_entry(self, scene) -> str:
         return batch_entry(scene, getattr(self.ctx, "disk_emission_set", False), self._ring_f64(),
-                           self.emission_batch, self.disk_ring_batch)
+                           self.emission_batch, self.disk_ring_batch, self.disk_ring_any_mode)
 
     def render_batch(self, b: int, frames, scene=None, events=None, stream=None, first: int = 0,
                      scenes=None) -> None:
@@ -432,7 +457,8 @@ class ShardedFrame:
         geo_render_disk_ring_batch for a disk scene while set_disk_ring_f64
         is on; geo_render_disk_adaptive_batch for a GEO_MODE_ADAPTIVE |
         GEO_FLAG_DISK scene, with GEO_FLAG_SS4 or without, any shading, no
-        keyword), on `stream` (a handle;
+        keyword; with disk_ring_any_mode, geo_render_disk_adaptive_ring_batch
+        for such a scene while set_disk_ring_f64 is on), on `stream` (a handle;
         default the buffer's render stream).  scenes: one per frame (they may
         differ in r_obs only); default `scene` (or the object's) for all."""
         from ._lib import GeoFrame, GeoScene, check
@@ -580,7 +606,9 @@ class ShardedFrame:
         path draws a GEO_MODE_ADAPTIVE | GEO_FLAG_DISK scene through
         geo_render_disk_adaptive, and with GEO_FLAG_SS4 (which has no
         one-frame call) through geo_render_disk_adaptive_batch with one
-        frame."""
+        frame; with disk_ring_any_mode and set_disk_ring_f64 on, through
+        geo_render_disk_adaptive_ring and geo_render_disk_adaptive_ring_batch
+        likewise."""
         b, sub = (i // self.K) % 2, i % self.K
         if sub == 0:
             self._retire(b)  # the batch that used this buffer two batches ago
@@ -610,9 +638,9 @@ class ShardedFrame:
             sref = self._scene_ref if scene is None else ctypes.byref(scene)
             total = None if steps_total is None else steps_total.data_ptr()
             # (the hot path reads one field: only an adaptive scene can be the adaptive disk's)
-            name = "geo_render_band_set" if sc.mode != self._adaptive else frame_entry(sc, self._ring_f64())
-            if name == "geo_render_disk_adaptive_batch":
-                st = lib.geo_render_disk_adaptive_batch(
+            name = "geo_render_band_set" if sc.mode != self._adaptive else self._frame_entry(sc)
+            if name.endswith("_batch"):  # (the adaptive disk's batched calls, with one frame)
+                st = getattr(lib, name)(
                     self._ctx_h, fref, sref, 1, self.width, self.height, band_h, row0, cycle, nb,
                     self._lv[b][sub], self.slice, total, sh)
             else:

@@ -131,6 +131,16 @@ LDS copy, on lanes that all take the f32 path.
 
   python tools/bench_disk.py --adaptive --ring [--out profiles/disk_adaptive_ring_bench.json]
   python tools/bench_disk.py --adaptive --ring --camera-away [--out profiles/disk_adaptive_ring_away_bench.json]
+
+--batch K --adaptive --ring measures the batched launch of adaptive disk frames
+with the f64 band (geo_render_disk_adaptive_ring_batch, geo_set_disk_ring_f64
+on) by --batch K --adaptive's method and on its layout and scene: one launch of
+K frames alternates with K one-frame geo_render_disk_adaptive_ring launches of
+the same frames back to back (the yardstick), unshaded and with --emission's
+state, each side on its own context, by both timings.  The totals are in the
+ring renders' mixed units (adaptive attempts outside the band, f64 steps in it).
+
+  python tools/bench_disk.py --batch 8 --adaptive --ring [--out profiles/disk_adaptive_ring_batch_bench.json]
 """
 from __future__ import annotations
 
@@ -170,11 +180,11 @@ def main():
                    help="with --adaptive --ring: the camera turned away from the hole, a frame with no band pixel")
     p.add_argument("--out")
     args = p.parse_args()
-    if args.adaptive and (args.emission or args.shift or (args.ring and args.batch)):
-        raise SystemExit("--adaptive goes alone, with --ring, or with --batch K")
+    if args.adaptive and (args.emission or args.shift or (args.camera_away and args.batch)):
+        raise SystemExit("--adaptive goes alone, with --ring, with --batch K, or with both")
     if not args.out:
         if args.adaptive and args.batch:
-            name = "disk_adaptive_batch_bench.json"
+            name = "disk_adaptive_ring_batch_bench.json" if args.ring else "disk_adaptive_batch_bench.json"
         elif args.adaptive and args.ring:
             name = "disk_adaptive_ring_away_bench.json" if args.camera_away else "disk_adaptive_ring_bench.json"
         elif args.adaptive:
@@ -1164,6 +1174,10 @@ def adaptive_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission):
     frames = (_lib.GeoFrame * K)(*([frame] * K))
     scenes = (_lib.GeoScene * K)(*([scene] * K))
     lib = _lib.lib
+    # --ring: the same sides with geo_set_disk_ring_f64 on, through the calls that draw the band
+    batch_name = "geo_render_disk_adaptive_ring_batch" if args.ring else "geo_render_disk_adaptive_batch"
+    single_name = "geo_render_disk_adaptive_ring" if args.ring else "geo_render_disk_adaptive"
+    batch_fn, single_fn = getattr(lib, batch_name), getattr(lib, single_name)
 
     def make_ctx(emit):
         c = g.Context(0)
@@ -1171,19 +1185,19 @@ def adaptive_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission):
         c.set_disk(tex, 1.6 * cfg.rs, 2.2 * cfg.rs)
         if emit:
             c.set_disk_emission(ramp, **emission)
+        c.set_disk_ring_f64(bool(args.ring))
         return c
 
     def run_batch(c, pairs=None):
         if pairs is not None:
             c.time_next_render(*pairs[0])
-        _lib.check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
-            c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
+        _lib.check(batch_name, batch_fn(c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, None, sh))
 
     def run_singles(c, pairs=None):
         for k in range(K):
             if pairs is not None:
                 c.time_next_render(*pairs[k])
-            _lib.check("geo_render_disk_adaptive", lib.geo_render_disk_adaptive(
+            _lib.check(single_name, single_fn(
                 c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None,
                 None, None, sh))
 
@@ -1233,14 +1247,21 @@ def adaptive_batch_session(args, cfg, frame, scene, sky, tex, ramp, emission):
     tot_b = torch.zeros(1, dtype=torch.int64, device=dev)
     tot_s = torch.zeros(1, dtype=torch.int64, device=dev)
     c = sides[0][1]
-    _lib.check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
-        c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, tot_b.data_ptr(), sh))
+    _lib.check(batch_name, batch_fn(c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, tot_b.data_ptr(), sh))
     for k in range(K):
-        _lib.check("geo_render_disk_adaptive", lib.geo_render_disk_adaptive(
+        _lib.check(single_name, single_fn(
             c._h, ctypes.byref(frame), ctypes.byref(scene), W, H, *band, out.data_ptr() + k * packed, None, None, None,
             tot_s.data_ptr(), sh))
     torch.cuda.synchronize()
+    # (--ring: mixed units, adaptive attempts outside the band and fixed f64 steps inside it)
     res["attempts_total_batch"], res["attempts_total_singles"] = int(tot_b.item()), int(tot_s.item())
+    if args.ring:  # the band's share of the frames: the same frames' attempts with the state off
+        c.set_disk_ring_f64(False)
+        tot_o = torch.zeros(1, dtype=torch.int64, device=dev)
+        _lib.check("geo_render_disk_adaptive_batch", lib.geo_render_disk_adaptive_batch(
+            c._h, frames, scenes, K, W, H, *band, out.data_ptr(), packed, tot_o.data_ptr(), sh))
+        torch.cuda.synchronize()
+        res["attempts_total_batch_state_off"] = int(tot_o.item())
     for _, c, *_ in sides:
         c.close()
     return res
@@ -1276,8 +1297,11 @@ def adaptive_batch_main(args):
         "frames_per_batch": K, "n": args.n, "alternations": args.alternations, "settle": args.settle,
         "order_in_a_sample": ["plain_batch", "plain_single", "emission_batch", "emission_single"],
         "warmup": args.warmup,
-        "timing": "stream_events: a pair of events on the stream around one geo_render_disk_adaptive_batch call of K "
-                  "frames, or around K one-frame geo_render_disk_adaptive launches back to back; dispatch_events: "
+        "ring_f64": bool(args.ring),
+        "calls": (["geo_render_disk_adaptive_ring_batch", "geo_render_disk_adaptive_ring"] if args.ring else
+                  ["geo_render_disk_adaptive_batch", "geo_render_disk_adaptive"]),
+        "timing": "stream_events: a pair of events on the stream around one batched call (calls[0]) of K "
+                  "frames, or around K one-frame launches (calls[1]) back to back; dispatch_events: "
                   "geo_time_next_render pairs on the render dispatches alone, the K one-frame times added; the four "
                   "sides (unshaded and emission, batch and one-frame) alternate, each on its own context; per "
                   "alternation the median of n, after settle alternations of each timing that are kept apart; spread = "

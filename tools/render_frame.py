@@ -9,7 +9,7 @@ the present step of the absent wgpu_renderer loop.
   python tools/render_frame.py out.jpg --disk 1.6 2.2 [--cpu] [--pos 2.4 0 0.7 --camera 3.1416 -0.28]
         [--disk-shift SPIN EXP GAIN] [--ss]
         [--disk-emission T_REF T_LO T_HI EXPOSURE [--disk-profile power|thin] [--disk-spin 1|-1]]
-        [--disk-ring-f64] [--adaptive [--tol T] [--ss | --disk-ring-f64]]
+        [--disk-ring-f64] [--adaptive [--tol T] [--ss] [--disk-ring-f64]]
 
 --disk R_IN R_OUT draws the ray-traced thin accretion disk (GEO_FLAG_DISK:
 the sky sphere alone plus the textured disk with its secondary and third
@@ -26,18 +26,19 @@ scenes.blackbody_ramp from T_LO to T_HI, brightness EXPOSURE (T_obs/T_REF)**4);
 it takes the place of --disk-shift and works with --cpu and --ss.
 --disk-ring-f64 takes the pixels of the capture band through the f64 path
 (geo_set_disk_ring_f64: the third image's radii and colours to the disk's
-accuracy bar), on the GPU or with --cpu, not with --ss.
+accuracy bar), on the GPU or with --cpu, with --ss only beside --adaptive.
 --adaptive draws the disk frame with the error-controlled integrator
 (GEO_MODE_ADAPTIVE through geo_render_disk_adaptive, --tol its tolerance in u,
 0 = the default 1e-6), unshaded, with --disk-shift or with --disk-emission, on
 the GPU or with --cpu.  With --disk-ring-f64 the frame goes through
 geo_render_disk_adaptive_ring (--cpu: geo_render_cpu_disk_adaptive_ring_f64):
-the capture band's pixels in f64, the rest by the adaptive integrator; not
-together with --ss.  With --ss the GPU frame goes
-through geo_render_disk_adaptive_batch with one frame (the only call that
-supersamples an adaptive disk frame), and --cpu renders
-geo_render_cpu_disk_adaptive at twice the size and box-resolves it here
-(GEO_FLAG_SS4's definition: the CPU function refuses the flag).
+the capture band's pixels in f64, the rest by the adaptive integrator.  With
+--ss the GPU frame goes through geo_render_disk_adaptive_batch with one frame
+(the only call that supersamples an adaptive disk frame; with --disk-ring-f64
+geo_render_disk_adaptive_ring_batch, likewise), and --cpu renders
+geo_render_cpu_disk_adaptive (geo_render_cpu_disk_adaptive_ring_f64) at twice
+the size and box-resolves it here (GEO_FLAG_SS4's definition: the CPU functions
+refuse the flag).
 
 Without texture files the synthetic equirect sky of the benchmarks is used for
 the sky sphere and the planet/cloud spheres are skipped.  Units: rs = 1 (the
@@ -147,7 +148,8 @@ def disk_frame(args):
         if args.adaptive and args.ss:  # (a whole frame of 8-row bands, the last one clipped)
             nb = (h + 7) // 8
             rgba = torch.empty(nb * 8 * w * 4, dtype=torch.uint8, device="cuda:0")
-            ctx.render_disk_adaptive_batch([frame], scene, w, h, 8, 0, 8, nb, rgba)
+            render = ctx.render_disk_adaptive_ring_batch if args.disk_ring_f64 else ctx.render_disk_adaptive_batch
+            render([frame], scene, w, h, 8, 0, 8, nb, rgba)
             rgba = rgba[:w * h * 4]
         elif args.adaptive and args.disk_ring_f64:
             ctx.render_disk_adaptive_ring(frame, scene, w, h, h, 0, h, 1, rgba)
@@ -194,11 +196,12 @@ def main():
     p.add_argument("--disk-profile", choices=("power", "thin"), default="thin", help="with --disk-emission")
     p.add_argument("--disk-spin", type=int, choices=(1, -1), default=1, help="with --disk-emission")
     p.add_argument("--disk-ring-f64", action="store_true",
-                   help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); not with --ss")
+                   help="with --disk: the capture band's pixels in f64 (geo_set_disk_ring_f64); with --ss only "
+                        "beside --adaptive")
     p.add_argument("--adaptive", action="store_true",
                    help="with --disk: the error-controlled integrator (geo_render_disk_adaptive; with --ss "
                         "geo_render_disk_adaptive_batch with one frame; with --disk-ring-f64 "
-                        "geo_render_disk_adaptive_ring)")
+                        "geo_render_disk_adaptive_ring; with both geo_render_disk_adaptive_ring_batch with one frame)")
     p.add_argument("--tol", type=float, default=0.0, help="with --adaptive: the tolerance in u (0 = 1e-6)")
     p.add_argument("--cpu", action="store_true", help="with --disk: the CPU path (libgeo_cpu.so)")
     p.add_argument("--ss", action="store_true", help="with --disk: 2 x 2 supersampling (GEO_FLAG_SS4)")
@@ -206,8 +209,9 @@ def main():
     p.add_argument("--camera", type=float, nargs=2, default=(math.pi, -0.28), help="with --disk: camera (phi, theta)")
     p.add_argument("--fov", type=float, default=math.pi / 2, help="with --disk")
     args = p.parse_args()
-    if args.disk_ring_f64 and (not args.disk or args.ss):
-        p.error("--disk-ring-f64 goes with --disk and without --ss (a supersampled disk frame refuses the state)")
+    if args.disk_ring_f64 and (not args.disk or (args.ss and not args.adaptive)):
+        p.error("--disk-ring-f64 goes with --disk, and with --ss only beside --adaptive (a supersampled direct disk "
+                "frame refuses the state)")
     if args.adaptive and not args.disk:
         p.error("--adaptive goes with --disk")
     if args.tol != 0.0 and not args.adaptive:
